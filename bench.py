@@ -44,7 +44,74 @@ def parse():
     ap.add_argument("--allow-torch-transport", action="store_true", help=argparse.SUPPRESS)  # (the default since round 5; kept so that old command lines still parse)
     ap.add_argument("--dry-run-cpu", action="store_true", help=argparse.SUPPRESS)  # tests/test_bench_dry_run.py: the script's own control flow (rank bookkeeping, collectives, transports, self-check, the JSON line) on CPU - gloo instead of RCCL, whatever library VOXELS_HIP_LIBRARY names instead of the HIP one.  Its numbers mean nothing and the line says so.
     ap.add_argument("--halo-every-step", action="store_true", help="N > 1 only: exchange the slab halo inside every timed step (as after an edit) instead of once before the steps")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (every LOD level's block infos and meshes, as Polygonizer.all_levels() returns them) to DIR/<name>.npy in float32 / float64, at most 64 MB in all: a fixed seeded sample of the rows beyond that (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BUDGET = 60 << 20  # --dump-outputs: under 64 MB, in decimal or binary megabytes
+
+
+def _dump_layout(dt):
+    """(float type, columns) of an array of dtype `dt` as --dump-outputs writes it: a structured array (vertices, block infos)
+    one row per element with its fields' components as columns, in order; an index array as one column.  Exact: vertex fields
+    are float32 or bytes (float32), block infos uint32 or float32 (float64), indices uint32 (float64)."""
+    if dt.names is None:
+        return np.float64, 1
+    ft = np.float32 if all(dt[f].base in (np.float32, np.uint8) for f in dt.names) else np.float64
+    return ft, sum(int(np.prod(dt[f].shape)) for f in dt.names)
+
+
+def _dump_columns(a):
+    ft, cols = _dump_layout(a.dtype)
+    if a.dtype.names is None:
+        return a.astype(ft)
+    return np.concatenate([a[f].reshape(len(a), int(np.prod(a.dtype[f].shape))).astype(ft) for f in a.dtype.names], axis=1)
+
+
+def dump_outputs(out_dir, levels, prefix="", budget=DUMP_BUDGET, seed=0):
+    """--dump-outputs: per LOD level l the arrays a caller of the timed path receives (Polygonizer.all_levels()) as
+    <prefix>L<l>_{infos,verts,idx,tverts,tidx}.npy - block infos and vertices one row per element with their fields' components
+    as columns (id, n_verts, n_idx, n_tverts[6], n_tidx[6], min_corner[3], max_corner[3]; pos[3], sec[4], nrm[3], tex[8]) - and
+    <prefix>counts.npy (per level: blocks, vertices, indices, transition vertices, transition indices); an array without
+    elements is not written, its count says so.  When everything would
+    exceed `budget` bytes, the block infos are written whole (if they take at most an eighth of it) and of every other array
+    the same fraction of its rows, drawn without replacement by a RandomState seeded from `seed` and the file's name,
+    in ascending order, with the row numbers in <name>_rows.npy.  Returns the bytes written."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = []  # (name, array, bytes per row as written)
+    for l, lv in enumerate(levels):
+        for what, a in (("infos", lv.infos), ("verts", lv.verts), ("idx", lv.idx), ("tverts", lv.tverts), ("tidx", lv.tidx)):
+            if len(a):  # (an empty array - level 0 has no transition meshes - is only a zero in counts.npy)
+                ft, cols = _dump_layout(a.dtype)
+                arrays.append(("%sL%d_%s" % (prefix, l, what), a, np.dtype(ft).itemsize * cols))
+    counts = np.array([[len(lv.infos), len(lv.verts), len(lv.idx), len(lv.tverts), len(lv.tidx)] for lv in levels], np.float64)
+    room = budget - counts.nbytes - 128 * (2 * len(arrays) + 1)  # (.npy headers)
+    whole, frac = set(), 1.0
+    if sum(len(a) * b for _, a, b in arrays) > room:
+        infos = [(n, a, b) for n, a, b in arrays if n.endswith("_infos")]
+        whole = set(n for n, _, _ in infos) if sum(len(a) * b for _, a, b in infos) <= budget // 8 else set()
+        room -= sum(len(a) * b for n, a, b in arrays if n in whole)
+        frac = max(0.0, room / float(sum(len(a) * (b + 8) for n, a, b in arrays if n not in whole)))
+    written = 0
+
+    def save(name, x):
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, x)
+        return os.path.getsize(path)
+    written += save(prefix + "counts", counts)
+    for name, a, _ in arrays:
+        if name in whole or frac >= 1.0:
+            written += save(name, _dump_columns(a))
+            continue
+        k = max(1, int(len(a) * frac))
+        rows = np.sort(np.random.RandomState((seed + zlib.crc32(name.encode())) & 0xFFFFFFFF).choice(len(a), k, replace=False))
+        written += save(name, _dump_columns(a[rows]))
+        written += save(name + "_rows", rows.astype(np.float64))
+    return written
 
 
 def mem_available_gb():
@@ -301,6 +368,10 @@ def main():
         dist_pkg.all_reduce(te, op=dist_pkg.ReduceOp.MAX)
         elapsed = float(te.item())
     ms_per_step = elapsed / args.steps * 1e3
+    # what the last timed step computed, before anything else runs on this context
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, poly.all_levels(), prefix="rank%d_" % rank if world > 1 else "", budget=DUMP_BUDGET // world)
 
     # N > 1: the other variant as well - a step that includes the halo exchange (what a run after an edit pays) when the
     # timed steps above ran without it, and the other way round.  Every rank runs the same sequence (no collective is
@@ -754,6 +825,8 @@ def main():
                        "cold": cold, "steady_state_uncached": uncached, "edit": edit},
             "roofline": roofline,
         }
+        if args.dump_outputs:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
         if world == 1 and not args.no_cpu_baseline and not args.serialize:
             de = dropin_e2e(poly)
             if de:

@@ -4,7 +4,8 @@
 
 Each fixture stores the exact input bytes (int8 distances, u8 material, u8 blend) and, per LOD level, the
 reference's block infos, vertices, indices, transition vertices/indices and the statistics, so the tests
-never need /root/reference at run time."""
+never need /root/reference at run time.  `make_golden.py digests` writes reference_digests.json instead: SHA-256 digests of
+the reference's results in the scenarios the oracle and drop-in tests compare live (tests/reference_cases.py)."""
 import hashlib
 import os
 import sys
@@ -13,6 +14,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))  # voxels_amd (vxo's material map, the synthetic inputs)
 import fields  # noqa: E402
 import vxo  # noqa: E402
 
@@ -77,5 +79,41 @@ def main():
     print("wrote quantize16.npz")
 
 
+def digests():
+    """tests/golden/reference_digests.json (tests/reference_cases.py): the reference's results of the oracle tests' scenarios,
+    and of the drop-in application (oracle/_ref/dropin_ref, built by __graft_entry__.build() next to the reference library)
+    in every configuration tests/test_dropin_cpp.py runs."""
+    import json
+    import subprocess
+    import tempfile
+    import reference_cases as rc
+    ref = vxo.load_ref()
+    assert ref is not None, "build oracle/_ref first (make -C oracle ref)"
+    exe = os.path.join(os.path.dirname(os.path.dirname(HERE)), "oracle", "_ref", "dropin_ref")
+    assert os.path.exists(exe), "build oracle/_ref/dropin_ref first (__graft_entry__.build())"
+    out = {"cases": {name: rc.record(run(ref)) for name, run in sorted(rc.CASES.items())}, "dropin_dumps": {}}
+    configs = [(64, "", False, 0), (128, "", False, 0), (64, "B", False, 0), (128, "B", False, 0), (128, "", True, 0),
+               (128, "B", True, 0), (64, "", True, 0), (64, "", False, 4), (128, "", True, 4), (128, "", False, 4)]
+    with tempfile.TemporaryDirectory() as tmp:
+        for n, variant, gentle, edits in configs:
+            env = dict(os.environ)
+            env.pop("DROPIN_GENTLE", None)
+            env.pop("DROPIN_EDITS", None)
+            if gentle:
+                env["DROPIN_GENTLE"] = "1"
+            if edits:
+                env["DROPIN_EDITS"] = str(edits)
+            path = os.path.join(tmp, "dump.bin")
+            subprocess.check_call([exe, str(n), path] + ([variant] if variant else []), env=env, timeout=600)
+            out["dropin_dumps"][rc.dropin_key(n, variant, gentle, edits)] = rc.file_record(path)
+    with open(rc.GOLDEN, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("wrote", rc.GOLDEN)
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["digests"]:
+        digests()
+    else:
+        main()

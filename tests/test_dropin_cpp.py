@@ -1,15 +1,36 @@
 """Drop-in test of the C++ API: tests/cpp/dropin_test.cpp, written only against the reference's public API, built
 against (a) the reference's headers + the unmodified reference library and (b) this repo's include/ + libVoxels.so.
 Both binaries must write byte-identical dumps (all levels, blocks, vertices, indices, statistics, the modification's
-block ids, block accessors, the packed grid).  (a) is built where /root/reference exists and travels in oracle/_ref."""
+block ids, block accessors, the packed grid).  (a) is built where /root/reference exists and travels in oracle/_ref; the
+digests of its dumps are stored in tests/golden/reference_digests.json (tests/reference_cases.py), so that (b) is checked
+against the reference's bytes everywhere."""
 import os
 import subprocess
 
 import pytest
 
+import reference_cases
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OURS = os.path.join(ROOT, "tests", "cpp", "dropin_ours")
 REF = os.path.join(ROOT, "oracle", "_ref", "dropin_ref")
+
+
+def assert_reference_bytes(ours, tmp_path, n, variant, env):
+    """`ours` holds, byte for byte, the dump the reference build of the same application writes with the same arguments and
+    environment: compared with a live run of oracle/_ref/dropin_ref where it was built (whose dump must then also be the
+    stored one), and with the stored digests of the reference's dump in any case."""
+    key = reference_cases.dropin_key(n, variant, "DROPIN_GENTLE" in env, int(env.get("DROPIN_EDITS", "0")))
+    if os.path.exists(REF):
+        b = str(tmp_path / "ref.bin")
+        subprocess.check_call([REF, str(n), b] + ([variant] if variant else []), env=env, timeout=300)
+        da, db = open(ours, "rb").read(), open(b, "rb").read()
+        assert len(da) == len(db), (len(da), len(db))
+        if da != db:
+            first = next(i for i in range(len(da)) if da[i] != db[i])
+            raise AssertionError("dumps differ at byte %d of %d" % (first, len(da)))
+        reference_cases.assert_dump_is_the_reference_s(b, key)
+    reference_cases.assert_dump_is_the_reference_s(ours, key)
 
 
 def test_public_headers_compile_standalone(tmp_path):
@@ -29,17 +50,10 @@ def test_same_application_same_bytes(tmp_path, n, variant):
     from voxels_amd import build
     build.build_cpp_api()
     build.build_dropin_tests()
-    if not os.path.exists(REF):
-        pytest.skip("oracle/_ref/dropin_ref not built (needs /root/reference at build time)")
-    a, b = str(tmp_path / "ours.bin"), str(tmp_path / "ref.bin")
+    a = str(tmp_path / "ours.bin")
     extra = [variant] if variant else []
     subprocess.check_call([OURS, str(n), a] + extra)
-    subprocess.check_call([REF, str(n), b] + extra)
-    da, db = open(a, "rb").read(), open(b, "rb").read()
-    assert len(da) == len(db), (len(da), len(db))
-    if da != db:
-        first = next(i for i in range(len(da)) if da[i] != db[i])
-        raise AssertionError("dumps differ at byte %d of %d" % (first, len(da)))
+    assert_reference_bytes(a, tmp_path, n, variant, dict(os.environ))
 
 
 @pytest.mark.gpu
@@ -52,17 +66,10 @@ def test_same_application_same_bytes_on_several_devices(tmp_path, n, devices, va
     from voxels_amd import build
     build.build_cpp_api()
     build.build_dropin_tests()
-    if not os.path.exists(REF):
-        pytest.skip("oracle/_ref/dropin_ref not built (needs /root/reference at build time)")
-    a, b = str(tmp_path / "ours.bin"), str(tmp_path / "ref.bin")
+    a = str(tmp_path / "ours.bin")
     extra = [variant] if variant else []
     subprocess.check_call([OURS, str(n), a] + extra, env=dict(os.environ, VOXELS_DEVICES=str(devices)), timeout=300)
-    subprocess.check_call([REF, str(n), b] + extra, timeout=300)
-    da, db = open(a, "rb").read(), open(b, "rb").read()
-    assert len(da) == len(db), (len(da), len(db))
-    if da != db:
-        first = next(i for i in range(len(da)) if da[i] != db[i])
-        raise AssertionError("dumps differ at byte %d of %d" % (first, len(da)))
+    assert_reference_bytes(a, tmp_path, n, variant, dict(os.environ))
 
 
 @pytest.mark.gpu
@@ -75,21 +82,14 @@ def test_several_devices_split_the_levels(tmp_path, n, devices, variant):
     from voxels_amd import build
     build.build_cpp_api()
     build.build_dropin_tests()
-    if not os.path.exists(REF):
-        pytest.skip("oracle/_ref/dropin_ref not built (needs /root/reference at build time)")
-    a, b = str(tmp_path / "ours.bin"), str(tmp_path / "ref.bin")
+    a = str(tmp_path / "ours.bin")
     extra = [variant] if variant else []
     env = dict(os.environ, DROPIN_GENTLE="1")
     out = subprocess.run([OURS, str(n), a] + extra, env=dict(env, VOXELS_DEVICES=str(devices), VOXELS_TRACE="1"), timeout=300, capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-500:]
     meshed = [int(l.split("meshed from level")[1].split()[0]) for l in out.stderr.splitlines() if "meshed from level" in l]
     assert meshed and min(meshed) >= 1, "the primary meshed every level itself: %s" % out.stderr[-800:]
-    subprocess.check_call([REF, str(n), b] + extra, env=env, timeout=300)
-    da, db = open(a, "rb").read(), open(b, "rb").read()
-    assert len(da) == len(db), (len(da), len(db))
-    if da != db:
-        first = next(i for i in range(len(da)) if da[i] != db[i])
-        raise AssertionError("dumps differ at byte %d of %d" % (first, len(da)))
+    assert_reference_bytes(a, tmp_path, n, variant, env)
 
 
 @pytest.mark.gpu
@@ -102,19 +102,12 @@ def test_a_surface_edited_again_and_again(tmp_path, n, devices, gentle):
     from voxels_amd import build
     build.build_cpp_api()
     build.build_dropin_tests()
-    if not os.path.exists(REF):
-        pytest.skip("oracle/_ref/dropin_ref not built (needs /root/reference at build time)")
-    a, b = str(tmp_path / "ours.bin"), str(tmp_path / "ref.bin")
+    a = str(tmp_path / "ours.bin")
     env = dict(os.environ, DROPIN_EDITS="4")
     if gentle:
         env["DROPIN_GENTLE"] = "1"
     subprocess.check_call([OURS, str(n), a], env=dict(env, VOXELS_DEVICES=str(devices)), timeout=300)
-    subprocess.check_call([REF, str(n), b], env=env, timeout=300)
-    da, db = open(a, "rb").read(), open(b, "rb").read()
-    assert len(da) == len(db), (len(da), len(db))
-    if da != db:
-        first = next(i for i in range(len(da)) if da[i] != db[i])
-        raise AssertionError("dumps differ at byte %d of %d" % (first, len(da)))
+    assert_reference_bytes(a, tmp_path, n, "", env)
 
 
 @pytest.mark.gpu
