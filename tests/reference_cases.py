@@ -13,6 +13,7 @@ import os
 import numpy as np
 
 import fields
+import grid_sizes
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_digests.json")
 CHUNK = 1 << 20  # drop-in dumps: one digest per MiB besides the whole file's, so a mismatch still says where it starts
@@ -106,6 +107,50 @@ def terrain(o, seed, n):
     return [("levels", s.all_levels()), ("stats", s.stats())]
 
 
+def odd_sizes(o):
+    """Every edge of grid_sizes.ODD_SIZES (coarse levels covering a prefix of each axis): a terrain through the float path
+    and a full-range int8 noise field, with materials."""
+    out = []
+    for n in grid_sizes.ODD_SIZES:
+        f = fields.terrain_field(n, 60 + n)
+        m, b = fields.materials_for(n, 60 + n)
+        g = o.grid_from_float(f, m, b)
+        s = o.execute(g)
+        out += [("n=%d terrain flags" % n, g.block_flags()), ("n=%d terrain levels" % n, s.all_levels()),
+                ("n=%d terrain stats" % n, s.stats())]
+        s.destroy()
+        q = fields.quantize_full_range(fields.smooth_noise(n, 70 + n, scale=8, amp=3.0))
+        s = o.execute(o.grid_from_dense(q, m, b))
+        out += [("n=%d noise levels" % n, s.all_levels()), ("n=%d noise stats" % n, s.stats())]
+        s.destroy()
+    return out
+
+
+def odd_edits(o, n):
+    """grid_sizes.edit_chain at an edge that is not a power of two: after every brush the box, the incremental Execute's
+    modified ids, the levels and the statistics; at the end the grid's file and a full Execute."""
+    f = fields.terrain_field(n, 90 + n)
+    m, b = fields.materials_for(n, 90 + n)
+    g = o.grid_from_float(f, m, b)
+    s = o.execute(g)
+    out = []
+    for k, edit in enumerate(grid_sizes.edit_chain(n)):
+        box = grid_sizes.apply_edit(g, edit)
+        ids = o.execute_modify(g, s, *box)
+        out += [("edit %d box min" % k, box[0]), ("edit %d box max" % k, box[1]), ("edit %d modified ids" % k, ids),
+                ("edit %d levels" % k, s.all_levels()), ("edit %d stats" % k, s.stats())]
+    s2 = o.execute(g)
+    return out + [("pack", g.pack()), ("full run levels", s2.all_levels()), ("full run stats", s2.stats())]
+
+
+def odd_heightmap(o):
+    """Grid::Create(w, heightmap) at w = 80: dense data, flags, file bytes."""
+    n = 80
+    g = o.grid_from_heightmap(n, grid_sizes.heightmap_for(n, 8))
+    out = [("dense %s" % name, a) for name, a in zip(("dist", "mat", "blend"), g.read_dense())]
+    return out + [("flags", g.block_flags()), ("pack", g.pack())]
+
+
 CASES = {
     "live_small_21": lambda o: live_small(o, 21),
     "live_small_22": lambda o: live_small(o, 22),
@@ -115,6 +160,10 @@ CASES = {
     "heightmap": heightmap,
     "terrain_41_32": lambda o: terrain(o, 41, 32),
     "terrain_42_64": lambda o: terrain(o, 42, 64),
+    "odd_sizes": odd_sizes,
+    "odd_edits_80": lambda o: odd_edits(o, 80),
+    "odd_edits_208": lambda o: odd_edits(o, 208),
+    "odd_heightmap": odd_heightmap,
 }
 
 

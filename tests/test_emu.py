@@ -585,12 +585,13 @@ def test_emu_rejects_misaligned_slabs_and_oversized_grids(emu):
         make_poly(emu).attach(4096, 0, 4096, d.ctypes.data, 0, m.ctypes.data, m.ctypes.data, 0, flags.ctypes.data)
 
 
-@pytest.mark.parametrize("world,axis", [(2, "z"), (2, "y"), (4, "y")])
+@pytest.mark.parametrize("world,axis", [(2, "z"), (2, "y"), (4, "y"), (3, "z"), (3, "y")])
 def test_emu_halo_exchange_group(emu, world, axis):
-    """vx_halo_exchange_group (the C-ABI halo exchange with in-process transport): region logic + piece descriptors on the CPU."""
+    """vx_halo_exchange_group (the C-ABI halo exchange with in-process transport): region logic + piece descriptors on the CPU.
+    Three ranks: 192^3 in slabs of 64, an edge of which the reference's level 3 covers only 128."""
     import torch
     from voxels_amd import synth
-    n, levels = 128, 3 if world == 2 else 2
+    n, levels = {2: (128, 3), 3: (192, 2), 4: (128, 2)}[world]
     d, m, b = synth.terrain(n, 0, n, 7)
     whole = make_poly(emu)
     whole.upload(d, m, b, synth.block_empty_flags(d))
@@ -643,3 +644,110 @@ def test_emu_empty_surface_host_meshes(emu):
     assert hm.verts.size == 0 and hm.indices.size == 0
     assert all(p.level(l).totals() == (0, 0, 0, 0, 0) for l in range(info.levels))
     hm.release()
+
+
+# ---- edges that are not powers of two (tests/grid_sizes.py): coarse levels that cover only a prefix of each axis ----------
+
+def check_odd_size_runs(p, port, n, nrm_tol=0.0):
+    """A terrain with materials and a full-range noise field at edge n: every level, then each level limit, against the port."""
+    import grid_sizes
+    f = fields.terrain_field(n, 60 + n)
+    m, b = fields.materials_for(n, 60 + n)
+    q = fields.quantize_full_range(fields.smooth_noise(n, 70 + n, scale=8, amp=3.0))
+    for label, g in (("terrain", port.grid_from_float(f, m, b)), ("noise", port.grid_from_dense(q, m, b))):
+        assert check_all_level_limits(p, port, g, "n=%d %s" % (n, label), nrm_tol) == grid_sizes.ref_levels(n)
+
+
+def check_all_level_limits(p, port, g, label, nrm_tol=0.0):
+    """The grid `g` of the port uploaded dense: all levels (surface and statistics), then every level limit.  Returns the
+    number of levels."""
+    s = port.execute(g)
+    want = s.all_levels()
+    p.upload(*g.read_dense(), g.block_flags())
+    p.execute()
+    ok, msg = fields.surface_equal(p.all_levels(), want, nrm_tol=nrm_tol)
+    assert ok, "%s: %s" % (label, msg)
+    assert np.array_equal(p.stats(), s.stats()), label
+    for limit in range(1, len(want)):
+        p.execute(limit)
+        got = p.all_levels()
+        assert len(got) == limit, (label, limit)
+        ok, msg = fields.surface_equal(got, want[:limit], nrm_tol=nrm_tol)
+        assert ok, "%s, %d levels: %s" % (label, limit, msg)
+    return len(want)
+
+
+def check_edit_chain(p, port, n, nrm_tol=0.0, upload="dense"):
+    """grid_sizes.edit_chain applied by the library to its resident grid and by the port to its own: after every brush the
+    box, the rebuilt block ids, the surface and the statistics of the incremental run; at the end the grid file and a full run
+    (tests/reference_cases.py pins the port's side of this chain to the reference)."""
+    import grid_sizes
+    f = fields.terrain_field(n, 90 + n)
+    m, b = fields.materials_for(n, 90 + n)
+    g = port.grid_from_float(f, m, b)
+    s = port.execute(g)
+    if upload == "packed":
+        p.upload_packed(g.pack())
+    else:
+        p.upload(*g.read_dense(), g.block_flags())
+    p.execute()
+    changed = 0
+    for k, edit in enumerate(grid_sizes.edit_chain(n)):
+        pre = g.read_dense()[0]
+        mn, mx = grid_sizes.apply_edit(g, edit)
+        mn2, mx2 = grid_sizes.apply_edit(p, edit)
+        assert np.array_equal(mn, mn2) and np.array_equal(mx, mx2), "n=%d edit %d: box" % (n, k)
+        changed += int(not np.array_equal(pre, g.read_dense()[0]))
+        ref_ids = port.execute_modify(g, s, mn, mx)
+        got = p.execute_dirty(mn2, mx2)
+        assert np.array_equal(got, ref_ids), "n=%d edit %d %s: modified ids (%d vs %d)" % (n, k, edit, got.size, ref_ids.size)
+        ok, msg = fields.surface_equal(p.all_levels(), s.all_levels(), nrm_tol=nrm_tol)
+        assert ok, "n=%d edit %d %s: %s" % (n, k, edit, msg)
+        assert np.array_equal(p.stats(), s.stats()), "n=%d edit %d: stats" % (n, k)
+    assert changed >= len(grid_sizes.edit_chain(n)) // 2, "the chain must change the distances"
+    assert np.array_equal(p.pack(), g.pack()), "n=%d: grid file after the chain" % n
+    p.execute()
+    s = port.execute(g)
+    ok, msg = fields.surface_equal(p.all_levels(), s.all_levels(), nrm_tol=nrm_tol)
+    assert ok, "n=%d full run after the chain: %s" % (n, msg)
+    assert np.array_equal(p.stats(), s.stats())
+
+
+@pytest.mark.parametrize("n", [16, 48, 80, 112, 208])
+def test_emu_odd_sizes_every_level_limit(emu, port, n):
+    check_odd_size_runs(make_poly(emu), port, n)
+
+
+@pytest.mark.parametrize("n", [80, 208])
+def test_emu_odd_size_edit_chain(emu, port, n):
+    check_edit_chain(make_poly(emu), port, n, upload="packed" if n == 80 else "dense")
+
+
+def test_emu_odd_size_polygonize_from_then_edit(emu, port):
+    """vx_polygonize_from at 208^3 (the emulation meshes every level and says so), then a brush in the uncovered band."""
+    import grid_sizes
+    n = 208
+    f = fields.terrain_field(n, 5)
+    m, b = fields.materials_for(n, 5)
+    g = port.grid_from_float(f, m, b)
+    s = port.execute(g)
+    p = make_poly(emu)
+    p.upload(*g.read_dense(), g.block_flags())
+    info = p.execute_from(0, 2)
+    assert info.first_meshed_level == 0
+    ok, msg = fields.surface_equal(p.all_levels(), s.all_levels())
+    assert ok, msg
+    edit = grid_sizes.edit_chain(n)[0]
+    mn, mx = grid_sizes.apply_edit(g, edit)
+    grid_sizes.apply_edit(p, edit)
+    assert np.array_equal(p.execute_dirty(mn, mx), port.execute_modify(g, s, mn, mx))
+    ok, msg = fields.surface_equal(p.all_levels(), s.all_levels())
+    assert ok, msg
+    assert np.array_equal(p.stats(), s.stats())
+
+
+@pytest.mark.parametrize("n,noisy", [(80, False), (112, True)])
+def test_emu_odd_size_packed_round_trips(emu, port, n, noisy):
+    d, m, b = _packed_case(n, 21, noisy)
+    check_packed(lambda: make_poly(emu), port, d, m, b, "packed n=%d noisy=%s" % (n, noisy))
+    check_pack(make_poly(emu), port, n, 41, noisy)

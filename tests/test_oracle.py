@@ -144,3 +144,20 @@ def test_port_vs_reference_gpu_parity_inputs(port, ref, case):
     """The terrains tests/test_gpu_parity.py::test_hip_vs_oracle_terrain polygonizes: the port it compares the HIP path with
     gives the reference's bytes for them."""
     compare_with_reference(port, ref, case)
+
+
+def test_port_vs_reference_odd_sizes(port, ref):
+    """Edges 16, 48, 80, 112, 208 (tests/grid_sizes.py): coarse levels that cover only a prefix of each axis, a band meshed
+    by finer levels alone, transition faces toward a level that stops short - every level and the statistics."""
+    compare_with_reference(port, ref, "odd_sizes")
+
+
+@pytest.mark.parametrize("n", [80, 208])
+def test_port_vs_reference_odd_edits(port, ref, n):
+    """Brushes in the band the coarsest levels leave uncovered (the incremental Execute floors and clamps its dirty box per
+    level): boxes, modified ids, levels and statistics after each, then the grid file and a full Execute."""
+    compare_with_reference(port, ref, "odd_edits_%d" % n)
+
+
+def test_port_heightmap_constructor_odd_size(port, ref):
+    compare_with_reference(port, ref, "odd_heightmap")

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Randomised parity sweep of the HIP path against the oracle (not part of the test suite; run on the GPU box):
-terrains, full-range noise, zero-heavy fields, sparse bubbles and flat slabs with random materials, sizes 32..128,
+terrains, full-range noise, zero-heavy fields, sparse bubbles and flat slabs with random materials, sizes 32..128 (edges that are not powers of two among them),
 every level; with a third argument `edits`: random chains of device edits + incremental runs (VX_FUZZ_CHAIN = edits per
 chain, default 5; VX_FUZZ_N = grid size).
 Usage: python tools/fuzz_parity.py [seconds] [first_seed] [edits]"""
@@ -50,7 +50,7 @@ def fuzz_edits(oracle, p, budget, seed):
     t0, chains, edits = time.time(), 0, 0
     while time.time() - t0 < budget:
         rng = np.random.RandomState(seed)
-        n = int(os.environ["VX_FUZZ_N"]) if os.environ.get("VX_FUZZ_N") else int(rng.choice([32, 64, 64]))
+        n = int(os.environ["VX_FUZZ_N"]) if os.environ.get("VX_FUZZ_N") else int(rng.choice([32, 48, 64, 64, 80, 96, 112]))
         d, m, b = make_field(int(rng.choice([0, 1, 2])), n, seed)
         g = oracle.grid_from_dense(d, m, b)
         s = oracle.execute(g)
@@ -104,7 +104,7 @@ def main():
         return fuzz_edits(oracle, p, budget, seed)
     t0, runs, partial = time.time(), 0, 0
     while time.time() - t0 < budget:
-        kind, n = seed % 5, [32, 64, 64, 128][(seed // 5) % 4]
+        kind, n = seed % 5, [32, 48, 64, 64, 80, 96, 112, 128][(seed // 5) % 8]
         d, m, b = make_field(kind, n, seed)
         g = oracle.grid_from_dense(d, m, b)
         s = oracle.execute(g)

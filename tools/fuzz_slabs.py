@@ -40,7 +40,11 @@ def check_seed(seed):
     dev = torch.device("cuda", 0)
     whole, part = contexts()
     rng = np.random.RandomState(seed)
-    n, levels, world, axis = int(rng.choice([64, 128, 256])), int(rng.choice([1, 2, 3])), int(rng.choice([2, 4])), str(rng.choice(["z", "y"]))
+    if seed % 2:  # an odd number of ranks: 3 or 5 slabs of an edge that is not a power of two
+        n, world = [(96, 3), (192, 3), (384, 3), (160, 5), (320, 5)][int(rng.randint(0, 5))]
+        levels, axis = int(rng.choice([1, 2, 3])), str(rng.choice(["z", "y"]))
+    else:
+        n, levels, world, axis = int(rng.choice([64, 128, 256])), int(rng.choice([1, 2, 3])), int(rng.choice([2, 4])), str(rng.choice(["z", "y"]))
     if n % ((16 << (levels - 1)) * world):
         return None
     d, m, b = fz.make_field(int(rng.randint(0, 5)), n, seed + 1)

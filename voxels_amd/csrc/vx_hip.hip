@@ -781,7 +781,9 @@ __device__ __forceinline__ void pyramid_write_segment(const PyramidLevel* pyr, i
 		const PyramidLevel& P = pyr[l];
 		if (!P.data || ((y | z) & ((1 << l) - 1))) break;
 		if (!(xs & ((1 << l) - 1))) P.data[pyramid_offset(P, xs >> l, y >> l, z >> l)] = (i8)(d.x & 0xFFu);
-		if (FAR_X && xs + 16 == n) P.data[pyramid_offset(P, n >> l, y >> l, z >> l)] = (i8)(d.w >> 24);
+		// (the clamped far entry exists where 2^l divides n; elsewhere entry n >> l is the ordinary sample (n >> l) << l < n,
+		// which the line above has just written - a level that stops short of n reads it as its last blocks' far sample)
+		if (FAR_X && xs + 16 == n && !(n & ((1 << l) - 1))) P.data[pyramid_offset(P, n >> l, y >> l, z >> l)] = (i8)(d.w >> 24);
 	}
 }
 
@@ -811,7 +813,7 @@ __device__ __forceinline__ void lattice_far_x(const MirrorState& X, int n, int y
 #pragma unroll 1
 	for (int l = 0; l < PYRAMID_LEVELS; ++l) {
 		if ((y | z) & ((1 << l) - 1)) break;
-		if (l >= 1 && X.pyr[l].data) X.pyr[l].data[pyramid_offset(X.pyr[l], n >> l, y >> l, z >> l)] = (i8)last;
+		if (l >= 1 && X.pyr[l].data && !(n & ((1 << l) - 1))) X.pyr[l].data[pyramid_offset(X.pyr[l], n >> l, y >> l, z >> l)] = (i8)last; // (where 2^l divides n: pyramid_write_segment)
 		if (l < XPLANE_LEVELS && X.xp[l].data) X.xp[l].data[xplane_offset(X.xp[l], (u32)(n >> l) >> 5, (u32)(z >> l), (u32)(y >> l))] = (i8)last;
 	}
 }
@@ -1112,8 +1114,11 @@ __global__ __launch_bounds__(WG) void k_run_head(ExecParamsDev p, ResetRanges r,
 		if (lane == 0) waveActive[wave] = (u32)__popcll(m);
 		if (active) {
 			const u32 lx = threadIdx.x & 7u, ly = (threadIdx.x >> 3) & 7u, lz = threadIdx.x >> 6;
-			atomicOr(&below[1], 1u << ((lx >> 1) | ((ly >> 1) << 2) | ((lz >> 1) << 4)));
-			atomicOr(&below[2], 1u << ((lx >> 2) | ((ly >> 2) << 1)));
+			// a level-l ancestor exists inside the level's (L.cnt >> l)^3 blocks only: when n / 16 is not a power of two the last
+			// level-0 layers of an axis have none (their ids would alias other blocks of the level)
+			const u32 far = max(bx, max(by, bz));
+			if ((far >> 1) < (L.cnt >> 1)) atomicOr(&below[1], 1u << ((lx >> 1) | ((ly >> 1) << 2) | ((lz >> 1) << 4)));
+			if ((far >> 2) < (L.cnt >> 2)) atomicOr(&below[2], 1u << ((lx >> 2) | ((ly >> 2) << 1)));
 			below[0] = 1u;
 		}
 		__syncthreads();
@@ -1564,7 +1569,7 @@ __device__ __forceinline__ void mat_block(const ExecParamsDev& p, u32 level, u32
 	uint4 old0, old1;
 	if (!defineAll) { old0 = ((const uint4*)cacheOut)[tid]; old1 = ((const uint4*)cacheOut)[tid + WG]; }
 	const int x0 = (int)(bx * 16) * mult, y0 = (int)(by * 16) * mult, z0 = (int)(bz * 16) * mult;
-	const i8* base = g.dist + dist_offset(g, x0, y0, z0); // uniform; lanes add 32-bit offsets
+	const i8* base = g.dist + dist_offset(g, x0, y0, z0); // uniform; lanes add their sample's offset
 	const int pitch = g.pitchY;
 	const PyramidLevel& pyr = p.G.pyr[level < PYRAMID_LEVELS ? level : 0];
 	const bool lattice = level < PYRAMID_LEVELS && pyr.data != nullptr;
@@ -1595,7 +1600,8 @@ __device__ __forceinline__ void mat_block(const ExecParamsDev& p, u32 level, u32
 			if (sIdx < SAMPLES) {
 				const int i = sIdx % 17, j = (sIdx / 17) % 17, k = sIdx / 289;
 				const int dx = min(x0 + i * mult, n - 1) - x0, dy = min(y0 + j * mult, n - 1) - y0, dz = min(z0 + k * mult, n - 1) - z0;
-				v[q] = base[(u32)((dz * pitch + dy) * n + dx)];
+				// 64-bit: level 7 of a 2048^3 grid (no lattice copy) reaches 2047 planes of 2048^2 bytes past its base
+				v[q] = base[((size_t)dz * pitch + dy) * n + dx];
 			}
 		}
 #pragma unroll
