@@ -287,6 +287,54 @@ typedef struct vx_listed_block {
 	float min_corner[3], max_corner[3];
 } vx_listed_block;
 int vx_device_block_table(vx_ctx* ctx, uint32_t level, const vx_listed_block** d_table, uint32_t* n_blocks);
+
+/* ---- ray casts against the device-resident meshes ---------------------------------------------------------------------
+ * The nearest intersection of each ray with the triangles of the REGULAR meshes of one LOD level, as the last run on this
+ * context left them (the blocks of vx_device_block_table(level), vx_download_level order).  No reference counterpart: the
+ * reference leaves picking to the application over its host-resident meshes (doc_source/Rendering.md).
+ *   space   mesh space, the space of vx_vertex.pos: Y-up, voxel units.  vx_grid_inject_ball takes grid coordinates (Z-up):
+ *           swap y and z of a hit's pos before carving at it.
+ *   range   only hits with t_min <= t <= t_max count; t is in units of |dir| (dir need not be unit length).
+ *   faces   both faces of a triangle count (rays may start inside caves or inside solid); watertight test (Woop, Benthin,
+ *           Wald 2013): a ray through a shared edge or vertex of a closed part of the mesh does not pass through it.
+ *   ties    among hits at equal t the smallest (entry, tri) is reported.
+ *   misses  zero or NaN dir, NaN origin, t_min > t_max, or no triangle hit (a ray that never enters [0, n]^3 hits
+ *           nothing): t = +INF, entry = block_id = tri = UINT32_MAX, every other field 0.
+ *   scope   transition meshes and secondary positions are not intersected.
+ *   stale   after a grid edit, and until the next run, results describe the OLD meshes.
+ * The acceleration index of a level (block-coordinate -> entry map, per block a bucket sort of its triangles over its 4^3
+ * sub-bricks) is built on demand and goes stale with every full run, incremental run and vx_compact_pools on the context. */
+typedef struct vx_ray {
+	float origin[3];
+	float t_min;
+	float dir[3];
+	float t_max;
+} vx_ray;                 /* 32 bytes */
+typedef struct vx_ray_hit {
+	float t;              /* +INF on a miss */
+	float pos[3];         /* origin + t*dir, mesh space */
+	float nrm[3];         /* unit (v1-v0)x(v2-v0) of the hit triangle in index order, not flipped toward the ray */
+	float bary[2];        /* weights of the triangle's 2nd and 3rd vertex */
+	uint32_t entry;       /* index into the level's block table / vx_download_level order */
+	uint32_t block_id;    /* BlockPolygons::GetId of that block */
+	uint32_t tri;         /* triangle ordinal in the block's regular mesh: its indices 3*tri .. 3*tri+2 */
+} vx_ray_hit;             /* 48 bytes */
+typedef struct vx_ray_index_info {
+	uint64_t triangles;   /* regular triangles of the level */
+	uint64_t bytes;       /* device memory of the level's index (map, bucket starts, its share of the triangle permutation) */
+	uint32_t blocks;      /* entries of the level's block table */
+	uint32_t straddling;  /* triangles not inside the closed box of their sub-brick (+-1/256): must be 0 */
+	float build_ms;       /* device time of the last build of this level's index (HIP events) */
+} vx_ray_index_info;
+/* Builds the level's index, or keeps it if it is current; info (may be NULL) receives its figures. */
+int vx_raycast_prepare(vx_ctx* ctx, uint32_t level, vx_ray_index_info* info);
+/* Device arrays: enqueued on the context's stream (vx_set_stream), returns without waiting.  With a current index: no
+ * allocation, no copy, no synchronisation, one kernel launch; otherwise vx_raycast_prepare first. */
+int vx_raycast_device(vx_ctx* ctx, uint32_t level, const vx_ray* d_rays, uint32_t n, vx_ray_hit* d_hits);
+/* Host arrays, synchronous (picking). */
+int vx_raycast(vx_ctx* ctx, uint32_t level, const vx_ray* rays, uint32_t n, vx_ray_hit* hits);
+/* All three: VX_ERR_INVALID for a level at or beyond what the last run produced, a context without a surface, and null
+ * pointers with n > 0; n = 0 returns VX_OK and does nothing. */
 /* stats[0..3] = BlocksCalculated, TrivialCells, NonTrivialCells, DegenerateTrianglesRemoved; stats[4..19] =
  * PerCaseCellsCount (include/Polygonizer.h:110-132) */
 int vx_stats(vx_ctx* ctx, uint32_t stats[20]);

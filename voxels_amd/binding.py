@@ -16,6 +16,12 @@ BLOCK_INFO_DTYPE = np.dtype([
     ("n_tverts", "<u4", 6), ("n_tidx", "<u4", 6),
     ("min_corner", "<f4", 3), ("max_corner", "<f4", 3)])
 assert VERTEX_DTYPE.itemsize == 48 and BLOCK_INFO_DTYPE.itemsize == 84
+# vx_ray / vx_ray_hit (include/voxels_hip.h, ray casts)
+RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("t_min", "<f4"), ("dir", "<f4", 3), ("t_max", "<f4")])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("pos", "<f4", 3), ("nrm", "<f4", 3), ("bary", "<f4", 2),
+                      ("entry", "<u4"), ("block_id", "<u4"), ("tri", "<u4")])
+assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 48
+RAY_NONE = 0xFFFFFFFF
 
 
 class VoxelsHipError(RuntimeError):
@@ -53,6 +59,11 @@ class HostMeshes:
             self.release()
         except Exception:
             pass
+
+
+class RayIndexInfo(C.Structure):
+    _fields_ = [("triangles", C.c_uint64), ("bytes", C.c_uint64), ("blocks", C.c_uint32), ("straddling", C.c_uint32),
+                ("build_ms", C.c_float)]
 
 
 class ExecInfo(C.Structure):
@@ -136,6 +147,12 @@ class HipLibrary:
         lib.vx_stage_layout.argtypes = [vp, C.POINTER(C.c_int)]
         lib.vx_set_stage_timing.argtypes = [vp, C.c_int]
         lib.vx_stage_times.argtypes = [vp, vp]
+        # ray casts: HIP builds only (the CPU emulation library of the tests does not have them)
+        self.has_raycast = hasattr(lib, "vx_raycast")
+        if self.has_raycast:
+            lib.vx_raycast_prepare.argtypes = [vp, u32, vp]
+            lib.vx_raycast_device.argtypes = [vp, u32, vp, u32, vp]
+            lib.vx_raycast.argtypes = [vp, u32, vp, u32, vp]
         self.lib = lib
         self.path = path
         self.backend = lib.vx_backend().decode()
@@ -451,6 +468,42 @@ class Polygonizer:
         r = np.zeros(16, np.uint32)
         self._check(self._lib.vx_selftest(self._h, _ptr(r)), "vx_selftest")
         return r
+
+    def _ray_lib(self):
+        if not self._L.has_raycast:
+            raise VoxelsHipError("%s has no ray casts (vx_raycast*)" % self._L.path)
+        return self._lib
+
+    def raycast_prepare(self, level=0):
+        """vx_raycast_prepare: build the level's ray-cast index (or keep it if current); its figures as a dict."""
+        info = RayIndexInfo()
+        self._check(self._ray_lib().vx_raycast_prepare(self._h, int(level), C.byref(info)), "vx_raycast_prepare")
+        return {"triangles": int(info.triangles), "bytes": int(info.bytes), "blocks": int(info.blocks),
+                "straddling": int(info.straddling), "build_ms": float(info.build_ms)}
+
+    def raycast_device(self, d_rays, n, d_hits, level=0):
+        """vx_raycast_device: n rays at device address d_rays (RAY_DTYPE records, 16-byte aligned) -> d_hits (HIT_DTYPE), queued on
+        the context's stream (set_stream) without waiting.  Addresses are ints, e.g. tensor.data_ptr()."""
+        self._check(self._ray_lib().vx_raycast_device(self._h, int(level), C.c_void_p(d_rays), int(n), C.c_void_p(d_hits)), "vx_raycast_device")
+
+    def raycast_rays(self, rays, level=0):
+        """vx_raycast on a RAY_DTYPE array -> HIT_DTYPE array (synchronous)."""
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        hits = np.zeros(rays.size, HIT_DTYPE)
+        self._check(self._ray_lib().vx_raycast(self._h, int(level), _ptr(rays) if rays.size else None, rays.size,
+                                               _ptr(hits) if rays.size else None), "vx_raycast")
+        return hits
+
+    def raycast(self, origins, dirs, t_min=0.0, t_max=float("inf"), level=0):
+        """Nearest hit of each ray o + t d (t_min <= t <= t_max, t in units of |d|) with the regular meshes of one level, in
+        mesh space (Y-up, voxels): a HIT_DTYPE array (misses: t = inf, entry = block_id = tri = RAY_NONE)."""
+        origins = np.asarray(origins, np.float32).reshape(-1, 3)
+        dirs = np.asarray(dirs, np.float32).reshape(-1, 3)
+        n = max(len(origins), len(dirs))
+        rays = np.zeros(n, RAY_DTYPE)
+        rays["origin"], rays["dir"] = origins, dirs
+        rays["t_min"], rays["t_max"] = t_min, t_max
+        return self.raycast_rays(rays, level)
 
     def stats(self):
         out = np.zeros(20, np.uint32)

@@ -4096,3 +4096,4 @@ struct Backend {
 } // namespace
 
 #include "vx_host.inl"
+#include "vx_ray.inl"

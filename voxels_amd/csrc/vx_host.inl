@@ -135,6 +135,12 @@ struct vx_ctx {
 	u32 runEpoch = 0;           // tag of the current full run in LevelDesc::matDone (Globals::epoch)
 	u32 poolSlack = 1u << 16;   // VX_POOL_SLACK (read once at context creation; tests): the vertices of headroom the pool rules add - smallest pool, packing threshold, room for edits (indices: four times as many)
 	bool hostTiming = false;    // VX_HOST_TIMING (read once at context creation): print where a vx_polygonize call spends host time
+	// ray casts (vx_ray.inl): every full run, incremental run and pool compaction counts up meshEpoch (the pools may come back at
+	// the same address, so pointers say nothing); fullRunEpoch = its value after the last full run (the block tables' counts are
+	// then the run's device header words)
+	uint64_t meshEpoch = 0, fullRunEpoch = ~0ull;
+	void* rayState = nullptr;
+	void (*rayFree)(vx_ctx*) = nullptr;
 };
 
 // every entry point makes the context's device the calling thread's current device (the HIP current device is per thread)
@@ -754,6 +760,7 @@ void vx_ctx_destroy(vx_ctx* c)
 	c->be.comm_destroy();
 	c->be.free_pinned(c->hdrPinned);
 	c->be.free(c->dScratch);
+	if (c->rayFree) c->rayFree(c);
 	c->be.shutdown();
 	delete c;
 }
@@ -1434,6 +1441,7 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 	VX_ENTER(c);
 	if (!c || !c->n || !c->dDist) return fail(c, VX_ERR_INVALID, "vx_polygonize: no grid resident (call vx_grid_upload / vx_grid_attach first)");
 	if (!ensure_level_tables(c)) return fail(c, VX_ERR_DEVICE, "vx_polygonize: level table allocation failed: " + c->be.error());
+	++c->meshEpoch;
 	float mirrorMs = 0.f;
 	{
 		const bool stale = c->bricksStale;
@@ -1565,6 +1573,7 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 	c->listsReady = false; // the host copy of the block lists is fetched on first access
 	c->liveKnown = false;
 	c->deviceLists = true;
+	c->fullRunEpoch = c->meshEpoch;
 	u32 idBase = 0;
 	u32 blocksCalculated = 0, trivial = 0;
 	for (u32 L = 0; L < levels; ++L) {
@@ -1724,6 +1733,7 @@ int vx_compact_pools(vx_ctx* c)
 {
 	VX_ENTER(c);
 	if (!c || !c->haveSurface) return fail(c, VX_ERR_INVALID, "vx_compact_pools: no surface");
+	++c->meshEpoch;
 	if (ensure_lists(c) != VX_OK) return VX_ERR_DEVICE;
 	uint64_t liveV, liveI;
 	live_totals(c, liveV, liveI);
@@ -1812,6 +1822,7 @@ int vx_polygonize_dirty(vx_ctx* c, const float min_corner[3], const float max_co
 	auto tUs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count() * 1e-3; };
 	const auto t0 = tNow(); // (VX_HOST_TIMING: where the call's host time goes)
 	auto t1 = t0, t2 = t0, t3 = t0, t4 = t0;
+	++c->meshEpoch;
 	if (ensure_lists(c, false) != VX_OK) return VX_ERR_DEVICE;
 	if (!ensure_bricks(c)) return fail(c, VX_ERR_DEVICE, "vx_polygonize_dirty: brick mirror allocation failed: " + c->be.error());
 	// the new blocks' meshes are appended behind what the pools already hold: every kept block stays where it is;
