@@ -335,6 +335,77 @@ int vx_raycast_device(vx_ctx* ctx, uint32_t level, const vx_ray* d_rays, uint32_
 int vx_raycast(vx_ctx* ctx, uint32_t level, const vx_ray* rays, uint32_t n, vx_ray_hit* hits);
 /* All three: VX_ERR_INVALID for a level at or beyond what the last run produced, a context without a surface, and null
  * pointers with n > 0; n = 0 returns VX_OK and does nothing. */
+
+/* ---- LOD selection: which block of which level to draw, with indirect draw lists -----------------------------------------
+ * Each frame a renderer picks, per region, one level's block, frustum-culls it and draws the transition meshes of the faces
+ * where it meets a finer block (doc_source/Rendering.md of the reference leaves this to the client).  These entry points do
+ * it next to the block tables and write draw-indexed-indirect commands.  Mesh space (Y-up, voxels) throughout.
+ *   nodes      R = the reference's level count (log2(n/16) + 1, rounded down), T = levels of the last run - 1.  Level L has
+ *              cnt_L = (n/16) >> L nodes per axis; node (L, c) covers the internal (Z-up) box [c s, (c+1) s]^3, s = 16 * 2^L,
+ *              and the mesh-space box with y and z swapped (what vx_listed_block.min_corner / max_corner report).  Its parent
+ *              is (L+1, c >> 1) when L < T and c >> 1 < cnt_{L+1} on every axis; otherwise it is a root.  The roots of all
+ *              levels partition [0, n)^3 (sizes whose n/16 is not a power of two have bands only finer levels cover).
+ *   selection  O = the least set of opened nodes (levels >= 1) with
+ *              (1) distance: ranges[L] > 0 and d^2 < ranges[L] * ranges[L]  ->  node in O;
+ *              (2) closure: X in O and X has a parent  ->  parent(X) in O;
+ *              (3) balance: X active at level L >= 1 (a root, or its parent in O) and a leaf of level <= L - g(L) shares a face
+ *                  area with X  ->  X in O; g(L) = 1 for L = R - 1 (no transition meshes), 2 otherwise.
+ *              The leaves (active nodes not in O) are the selection; it is purely spatial (n, R, T, camera, ranges).
+ *   distance   float32, no contraction: d_a = max(max(min_a - cam_a, 0), cam_a - max_a); d^2 = (dx dx + dy dy) + dz dz.
+ *   drawn      a leaf whose level's block table has an entry for its coord_id, unless culled: for some plane (a, b, c, d)
+ *              (inside: a x + b y + c z + d >= 0), ((a px + b py) + c pz) + d < 0 in float32, p = the box corner that
+ *              maximises the plane (px = a >= 0 ? max.x : min.x, ...).  A culled leaf emits nothing.
+ *   faces      transitions bit f (BlockPolygons::TransitionFaceId order: -Y, -Z, -X, +Y, +Z, +X) = a leaf of a smaller level
+ *              (by (3): level L - 1, over the whole face) touches face f.  adjacency = the blockAdj of Rendering.md, in the bit
+ *              order of vertex.sec[3]: a regular vertex with bit b set lies on transition face b, so adjacency = transitions.
+ *   order      records by level, then by block-table entry.  Per record one regular command (i_count, 1, i_off, v_off,
+ *              record) and, in a second array, per set bit f with ti_count[f] > 0 one transition command (ti_count[f], 1,
+ *              ti_off[f], tv_off[f], record), in record order then face order.  first_instance = record index.
+ *   stale      tables, offsets and counts are those of the last run (vx_device_block_table).
+ * The selection keeps per-level node flags (about 1.14 (n/16)^3 bytes) and per-entry scratch on the device, allocated on first
+ * use and shared by every selection on the context: calls on one context must be ordered on one stream (a call queued on
+ * another stream, after vx_set_stream, may overwrite them while an earlier call still reads them). */
+typedef struct vx_lod_params {
+	float camera[3];          /* mesh space (Y-up), voxels */
+	uint32_t n_planes;        /* 0..6; 0 = no culling */
+	float planes[6][4];       /* (a, b, c, d): inside where a x + b y + c z + d >= 0 */
+	float ranges[16];         /* ranges[L] for L >= 1; <= 0: never split by distance; ranges[0] ignored */
+} vx_lod_params;              /* 176 bytes */
+typedef struct vx_lod_draw {
+	uint32_t level, entry;    /* the block: entry of vx_device_block_table(level) */
+	uint32_t block_id;        /* BlockPolygons::GetId */
+	uint32_t coord_id;        /* (bz * cnt + by) * cnt + bx, internal axes */
+	uint32_t transitions;     /* TransitionFaceId bits: faces that meet a finer leaf */
+	uint32_t adjacency;       /* blockAdj for the vertex shader (vertex.sec[3] bit order; equal to transitions) */
+	uint32_t reserved[2];     /* 0 */
+} vx_lod_draw;                /* 32 bytes */
+typedef struct vx_draw_indexed {  /* VkDrawIndexedIndirectCommand / D3D12_DRAW_INDEXED_ARGUMENTS */
+	uint32_t index_count, instance_count /* 1 */, first_index;
+	int32_t vertex_offset;
+	uint32_t first_instance;  /* record index */
+} vx_draw_indexed;            /* 20 bytes */
+typedef struct vx_lod_counts {
+	uint32_t records;         /* drawn leaves (what the arrays would hold with unlimited capacity) */
+	uint32_t regular;         /* regular commands (= records) */
+	uint32_t transition;      /* transition commands */
+	uint32_t leaves;          /* all leaves, meshed or not */
+	uint32_t meshed_leaves;   /* leaves with a block-table entry */
+	uint32_t culled_leaves;   /* meshed leaves the frustum culled */
+	uint64_t leaf_volume;     /* sum over leaves of 8^L in level-0 blocks: always (n/16)^3 */
+} vx_lod_counts;              /* 32 bytes */
+/* Device arrays (16-byte aligned), enqueued on the context's stream (vx_set_stream), returns without waiting: a handful of
+ * launches, no copy, no synchronisation, and no allocation once the node flags exist.  Always writes the full counts; fills
+ * the arrays up to their capacities (draw_capacity for draws and regular, transition_capacity for transition). */
+int vx_lod_select_device(vx_ctx* ctx, const vx_lod_params* params, uint32_t draw_capacity, uint32_t transition_capacity,
+                         vx_lod_draw* d_draws, vx_draw_indexed* d_regular, vx_draw_indexed* d_transition, vx_lod_counts* d_counts);
+/* Host arrays, synchronous.  VX_ERR_OVERFLOW (after writing the counts and the first `capacity` entries) when a capacity
+ * was too small; the levels' table entries summed are always enough for the draws. */
+int vx_lod_select(vx_ctx* ctx, const vx_lod_params* params, uint32_t draw_capacity, uint32_t transition_capacity,
+                  vx_lod_draw* draws, vx_draw_indexed* regular, vx_draw_indexed* transition, vx_lod_counts* counts);
+/* Both: VX_ERR_INVALID for a context without a surface, a last run that left levels unmeshed (vx_polygonize_from with
+ * first_meshed_level > 0), a NaN camera, plane or range, n_planes > 6, null params or counts, and null arrays with a
+ * non-zero capacity. */
+
 /* stats[0..3] = BlocksCalculated, TrivialCells, NonTrivialCells, DegenerateTrianglesRemoved; stats[4..19] =
  * PerCaseCellsCount (include/Polygonizer.h:110-132) */
 int vx_stats(vx_ctx* ctx, uint32_t stats[20]);

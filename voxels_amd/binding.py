@@ -22,6 +22,36 @@ HIT_DTYPE = np.dtype([("t", "<f4"), ("pos", "<f4", 3), ("nrm", "<f4", 3), ("bary
                       ("entry", "<u4"), ("block_id", "<u4"), ("tri", "<u4")])
 assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 48
 RAY_NONE = 0xFFFFFFFF
+# vx_lod_params / vx_lod_draw / vx_draw_indexed / vx_lod_counts (include/voxels_hip.h, LOD selection)
+LOD_PARAMS_DTYPE = np.dtype([("camera", "<f4", 3), ("n_planes", "<u4"), ("planes", "<f4", (6, 4)), ("ranges", "<f4", 16)])
+LOD_DRAW_DTYPE = np.dtype([("level", "<u4"), ("entry", "<u4"), ("block_id", "<u4"), ("coord_id", "<u4"), ("transitions", "<u4"),
+                           ("adjacency", "<u4"), ("reserved", "<u4", 2)])
+DRAW_INDEXED_DTYPE = np.dtype([("index_count", "<u4"), ("instance_count", "<u4"), ("first_index", "<u4"), ("vertex_offset", "<i4"),
+                               ("first_instance", "<u4")])
+LOD_COUNTS_DTYPE = np.dtype([("records", "<u4"), ("regular", "<u4"), ("transition", "<u4"), ("leaves", "<u4"),
+                             ("meshed_leaves", "<u4"), ("culled_leaves", "<u4"), ("leaf_volume", "<u8")])
+assert LOD_PARAMS_DTYPE.itemsize == 176 and LOD_DRAW_DTYPE.itemsize == 32
+assert DRAW_INDEXED_DTYPE.itemsize == 20 and LOD_COUNTS_DTYPE.itemsize == 32
+
+
+def lod_ranges(factor=4.0, levels=16):
+    """ranges[L] = factor * 16 * 2^L: a level-L block is split while the camera is closer than `factor` of its edges"""
+    r = np.zeros(16, np.float32)
+    r[:levels] = [factor * 16.0 * (1 << L) for L in range(levels)]
+    return r
+
+
+def lod_params(camera, ranges=None, planes=None):
+    """one LOD_PARAMS_DTYPE record (ranges: 16 floats, default lod_ranges(); planes: up to 6 (a, b, c, d) rows)"""
+    prm = np.zeros(1, LOD_PARAMS_DTYPE)
+    prm["camera"] = np.asarray(camera, np.float32).reshape(3)
+    r = lod_ranges() if ranges is None else np.asarray(ranges, np.float32).reshape(-1)
+    prm["ranges"][0, :len(r)] = r
+    if planes is not None:
+        pl = np.asarray(planes, np.float32).reshape(-1, 4)
+        prm["n_planes"] = len(pl)
+        prm["planes"][0, :min(len(pl), 6)] = pl[:6]
+    return prm
 
 
 class VoxelsHipError(RuntimeError):
@@ -153,6 +183,11 @@ class HipLibrary:
             lib.vx_raycast_prepare.argtypes = [vp, u32, vp]
             lib.vx_raycast_device.argtypes = [vp, u32, vp, u32, vp]
             lib.vx_raycast.argtypes = [vp, u32, vp, u32, vp]
+        # LOD selection: HIP builds only, likewise
+        self.has_lod = hasattr(lib, "vx_lod_select")
+        if self.has_lod:
+            lib.vx_lod_select_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
+            lib.vx_lod_select.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
         self.lib = lib
         self.path = path
         self.backend = lib.vx_backend().decode()
@@ -504,6 +539,39 @@ class Polygonizer:
         rays["origin"], rays["dir"] = origins, dirs
         rays["t_min"], rays["t_max"] = t_min, t_max
         return self.raycast_rays(rays, level)
+
+    def _lod_lib(self):
+        if not self._L.has_lod:
+            raise VoxelsHipError("%s has no LOD selection (vx_lod_select*)" % self._L.path)
+        return self._L.lib
+
+    def lod_select(self, camera, ranges=None, planes=None):
+        """vx_lod_select: (draws LOD_DRAW_DTYPE, regular DRAW_INDEXED_DTYPE, transition DRAW_INDEXED_DTYPE, counts dict) for a
+        mesh-space camera, ranges (16 floats, default lod_ranges()) and up to 6 frustum planes (a, b, c, d)."""
+        lib = self._lod_lib()
+        prm = lod_params(camera, ranges, planes)
+        cap = sum(self.device_block_table(L)[1] for L in range(self.info.levels)) if getattr(self, "info", None) else 0
+        tcap = cap
+        for attempt in range(2):
+            draws, regular = np.zeros(cap, LOD_DRAW_DTYPE), np.zeros(cap, DRAW_INDEXED_DTYPE)
+            transition, counts = np.zeros(tcap, DRAW_INDEXED_DTYPE), np.zeros(1, LOD_COUNTS_DTYPE)
+            rc = lib.vx_lod_select(self._h, _ptr(prm), cap, tcap, _ptr(draws) if cap else None, _ptr(regular) if cap else None,
+                                   _ptr(transition) if tcap else None, _ptr(counts))
+            if rc == -3 and attempt == 0:
+                cap, tcap = max(cap, int(counts["records"][0])), max(tcap, int(counts["transition"][0]))
+                continue
+            self._check(rc, "vx_lod_select")
+            break
+        c = {k: int(counts[k][0]) for k in LOD_COUNTS_DTYPE.names}
+        return draws[:c["records"]], regular[:c["records"]], transition[:c["transition"]], c
+
+    def lod_select_device(self, params, draw_capacity, transition_capacity, d_draws, d_regular, d_transition, d_counts):
+        """vx_lod_select_device: params = a LOD_PARAMS_DTYPE record (lod_params()), arrays at device addresses (ints, 16-byte
+        aligned); queued on the context's stream (set_stream), returns without waiting."""
+        prm = np.ascontiguousarray(params, LOD_PARAMS_DTYPE)
+        self._check(self._lod_lib().vx_lod_select_device(self._h, _ptr(prm), int(draw_capacity), int(transition_capacity),
+                                                         C.c_void_p(d_draws), C.c_void_p(d_regular), C.c_void_p(d_transition),
+                                                         C.c_void_p(d_counts)), "vx_lod_select_device")
 
     def stats(self):
         out = np.zeros(20, np.uint32)

@@ -4097,3 +4097,4 @@ struct Backend {
 
 #include "vx_host.inl"
 #include "vx_ray.inl"
+#include "vx_lod.inl"

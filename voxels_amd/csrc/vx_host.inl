@@ -141,6 +141,10 @@ struct vx_ctx {
 	uint64_t meshEpoch = 0, fullRunEpoch = ~0ull;
 	void* rayState = nullptr;
 	void (*rayFree)(vx_ctx*) = nullptr;
+	// LOD selection (vx_lod.inl): its device buffers, and the first level the last full run meshed (vx_polygonize_from)
+	void* lodState = nullptr;
+	void (*lodFree)(vx_ctx*) = nullptr;
+	u32 firstMeshedLevel = 0;
 };
 
 // every entry point makes the context's device the calling thread's current device (the HIP current device is per thread)
@@ -761,6 +765,7 @@ void vx_ctx_destroy(vx_ctx* c)
 	c->be.free_pinned(c->hdrPinned);
 	c->be.free(c->dScratch);
 	if (c->rayFree) c->rayFree(c);
+	if (c->lodFree) c->lodFree(c);
 	c->be.shutdown();
 	delete c;
 }
@@ -1566,6 +1571,7 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 		c->be.slowHint[0] = c->hdr[HDR_SLOW]; c->be.slowHint[1] = c->hdr[HDR_SLOW + 1];
 	}
 	c->levelsRun = levels;
+	c->firstMeshedLevel = emitFrom;
 	c->poolVerts = c->hdr[HDR_CURSORS]; c->poolIdx = c->hdr[HDR_CURSORS + CUR_I];
 	c->poolLineage = next_lineage(); // the pools were rewritten
 	c->haveSurface = true;
