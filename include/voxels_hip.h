@@ -336,6 +336,64 @@ int vx_raycast(vx_ctx* ctx, uint32_t level, const vx_ray* rays, uint32_t n, vx_r
 /* All three: VX_ERR_INVALID for a level at or beyond what the last run produced, a context without a surface, and null
  * pointers with n > 0; n = 0 returns VX_OK and does nothing. */
 
+/* ---- sphere casts and closest points against the device-resident meshes ----------------------------------------------
+ * Collision queries against the same triangles as the ray casts (no reference counterpart: doc_source/Rendering.md leaves
+ * collision to the application): where a sphere moving along a segment first touches the surface, and the nearest surface
+ * point within a distance.  They read the level's ray-cast index (vx_raycast_prepare) and need no memory of their own.
+ *   space   mesh space (Y-up, voxels), against the REGULAR triangles of one level as the last run on this context left them;
+ *           transition meshes are not queried.  After a grid edit, and until the next run, results describe the OLD meshes.
+ *   sphere  the hit is the least t in [t_min, t_max] at which dist(origin + t*dir, triangle) <= radius, over all triangles,
+ *           both faces; t is in units of |dir|.  A sphere that already touches a triangle at t_min hits at t = t_min with flag
+ *           VX_SPHERE_STARTED_IN_CONTACT and depth = radius - the least distance at t_min; contact and nrm then come from the
+ *           nearest triangle at t_min.  dir = 0 is allowed: a static overlap test at t_min.
+ *   misses  a NaN in origin or dir, a radius that is not finite or not > 0, t_min > t_max, or no contact: t = +INF,
+ *           entry = block_id = tri = UINT32_MAX, every other field 0.
+ *   closest the least distance from pos to any triangle, counted only if it is <= max_dist (which may be +INF: the whole
+ *           level).  NaN pos, or a NaN or negative max_dist, is a miss, encoded as for sphere casts (dist = +INF).
+ *   ties    among equal t (or equal dist) the smallest (entry, tri) is reported (at t_min: the nearest triangle first).
+ * Sizes are multiples of 16 bytes: device arrays must be 16-byte aligned. */
+#define VX_SPHERE_STARTED_IN_CONTACT 1u
+typedef struct vx_sphere_cast {
+	float origin[3];
+	float t_min;
+	float dir[3];
+	float t_max;
+	float radius;
+	float reserved[3];    /* 0 */
+} vx_sphere_cast;         /* 48 bytes */
+typedef struct vx_sphere_hit {
+	float t;              /* +INF on a miss */
+	float center[3];      /* origin + t*dir */
+	float contact[3];     /* the touched point of the triangle */
+	float nrm[3];         /* unit (center - contact); the face normal (index order) if the centre lies on the triangle */
+	float depth;          /* radius - distance at t_min when the cast starts in contact, else 0 */
+	uint32_t entry;       /* index into the level's block table / vx_download_level order */
+	uint32_t block_id;    /* BlockPolygons::GetId of that block */
+	uint32_t tri;         /* triangle ordinal in the block's regular mesh */
+	uint32_t flags;       /* bit 0: VX_SPHERE_STARTED_IN_CONTACT */
+	uint32_t reserved;    /* 0 */
+} vx_sphere_hit;          /* 64 bytes */
+typedef struct vx_point_query {
+	float pos[3];
+	float max_dist;
+} vx_point_query;         /* 16 bytes */
+typedef struct vx_point_hit {
+	float dist;           /* +INF when nothing lies within max_dist */
+	float point[3];       /* nearest point of the level's regular triangles */
+	float nrm[3];         /* unit (v1-v0)x(v2-v0) of that triangle, as vx_ray_hit.nrm */
+	float bary[2];        /* weights of its 2nd and 3rd vertex */
+	uint32_t entry, block_id, tri;
+} vx_point_hit;           /* 48 bytes */
+/* Device arrays: enqueued on the context's stream (vx_set_stream), returns without waiting.  With a current index: no
+ * allocation, no copy, no synchronisation, one kernel launch; otherwise vx_raycast_prepare first. */
+int vx_spherecast_device(vx_ctx* ctx, uint32_t level, const vx_sphere_cast* d_casts, uint32_t n, vx_sphere_hit* d_hits);
+/* Host arrays, synchronous. */
+int vx_spherecast(vx_ctx* ctx, uint32_t level, const vx_sphere_cast* casts, uint32_t n, vx_sphere_hit* hits);
+int vx_closest_point_device(vx_ctx* ctx, uint32_t level, const vx_point_query* d_q, uint32_t n, vx_point_hit* d_hits);
+int vx_closest_point(vx_ctx* ctx, uint32_t level, const vx_point_query* q, uint32_t n, vx_point_hit* hits);
+/* All four: VX_ERR_INVALID for a level at or beyond what the last run produced, a context without a surface, and null
+ * arrays with n > 0; n = 0 returns VX_OK and does nothing. */
+
 /* ---- LOD selection: which block of which level to draw, with indirect draw lists -----------------------------------------
  * Each frame a renderer picks, per region, one level's block, frustum-culls it and draws the transition meshes of the faces
  * where it meets a finer block (doc_source/Rendering.md of the reference leaves this to the client).  These entry points do

@@ -5,8 +5,10 @@ include/voxels_hip.h).  This package is the thin Python host side used by tests 
 the reference's operator interface for the path (Grid -> Polygonizer.Execute -> PolygonSurface levels/blocks)
 and fails loudly when the HIP library is missing — there is no CPU fallback.
 """
-from .binding import (BLOCK_INFO_DTYPE, DRAW_INDEXED_DTYPE, HIT_DTYPE, LOD_COUNTS_DTYPE, LOD_DRAW_DTYPE, RAY_DTYPE, VERTEX_DTYPE,
-                      HipLibrary, Level, Polygonizer, VoxelsHipError, hip_library_path, lod_params, lod_ranges)
+from .binding import (BLOCK_INFO_DTYPE, DRAW_INDEXED_DTYPE, HIT_DTYPE, LOD_COUNTS_DTYPE, LOD_DRAW_DTYPE, POINT_HIT_DTYPE,
+                      POINT_QUERY_DTYPE, RAY_DTYPE, SPHERE_CAST_DTYPE, SPHERE_HIT_DTYPE, VERTEX_DTYPE, HipLibrary, Level,
+                      Polygonizer, VoxelsHipError, hip_library_path, lod_params, lod_ranges)
 
-__all__ = ["BLOCK_INFO_DTYPE", "DRAW_INDEXED_DTYPE", "HIT_DTYPE", "LOD_COUNTS_DTYPE", "LOD_DRAW_DTYPE", "RAY_DTYPE", "VERTEX_DTYPE",
+__all__ = ["BLOCK_INFO_DTYPE", "DRAW_INDEXED_DTYPE", "HIT_DTYPE", "LOD_COUNTS_DTYPE", "LOD_DRAW_DTYPE", "POINT_HIT_DTYPE", "POINT_QUERY_DTYPE",
+           "RAY_DTYPE", "SPHERE_CAST_DTYPE", "SPHERE_HIT_DTYPE", "VERTEX_DTYPE",
            "HipLibrary", "Level", "Polygonizer", "VoxelsHipError", "hip_library_path", "lod_params", "lod_ranges"]

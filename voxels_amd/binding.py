@@ -22,6 +22,17 @@ HIT_DTYPE = np.dtype([("t", "<f4"), ("pos", "<f4", 3), ("nrm", "<f4", 3), ("bary
                       ("entry", "<u4"), ("block_id", "<u4"), ("tri", "<u4")])
 assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 48
 RAY_NONE = 0xFFFFFFFF
+# vx_sphere_cast / vx_sphere_hit / vx_point_query / vx_point_hit (include/voxels_hip.h, sphere casts and closest points)
+SPHERE_CAST_DTYPE = np.dtype([("origin", "<f4", 3), ("t_min", "<f4"), ("dir", "<f4", 3), ("t_max", "<f4"), ("radius", "<f4"),
+                              ("reserved", "<f4", 3)])
+SPHERE_HIT_DTYPE = np.dtype([("t", "<f4"), ("center", "<f4", 3), ("contact", "<f4", 3), ("nrm", "<f4", 3), ("depth", "<f4"),
+                             ("entry", "<u4"), ("block_id", "<u4"), ("tri", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+POINT_QUERY_DTYPE = np.dtype([("pos", "<f4", 3), ("max_dist", "<f4")])
+POINT_HIT_DTYPE = np.dtype([("dist", "<f4"), ("point", "<f4", 3), ("nrm", "<f4", 3), ("bary", "<f4", 2),
+                            ("entry", "<u4"), ("block_id", "<u4"), ("tri", "<u4")])
+assert SPHERE_CAST_DTYPE.itemsize == 48 and SPHERE_HIT_DTYPE.itemsize == 64
+assert POINT_QUERY_DTYPE.itemsize == 16 and POINT_HIT_DTYPE.itemsize == 48
+SPHERE_STARTED_IN_CONTACT = 1
 # vx_lod_params / vx_lod_draw / vx_draw_indexed / vx_lod_counts (include/voxels_hip.h, LOD selection)
 LOD_PARAMS_DTYPE = np.dtype([("camera", "<f4", 3), ("n_planes", "<u4"), ("planes", "<f4", (6, 4)), ("ranges", "<f4", 16)])
 LOD_DRAW_DTYPE = np.dtype([("level", "<u4"), ("entry", "<u4"), ("block_id", "<u4"), ("coord_id", "<u4"), ("transitions", "<u4"),
@@ -184,6 +195,12 @@ class HipLibrary:
             lib.vx_raycast_device.argtypes = [vp, u32, vp, u32, vp]
             lib.vx_raycast.argtypes = [vp, u32, vp, u32, vp]
         # LOD selection: HIP builds only, likewise
+        # sphere casts and closest points: HIP builds only, like the ray casts
+        self.has_shapecast = hasattr(lib, "vx_spherecast") and hasattr(lib, "vx_closest_point")
+        if self.has_shapecast:
+            for name in ("vx_spherecast_device", "vx_spherecast", "vx_closest_point_device", "vx_closest_point"):
+                getattr(lib, name).argtypes = [vp, u32, vp, u32, vp]
+                getattr(lib, name).restype = C.c_int
         self.has_lod = hasattr(lib, "vx_lod_select")
         if self.has_lod:
             lib.vx_lod_select_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
@@ -539,6 +556,59 @@ class Polygonizer:
         rays["origin"], rays["dir"] = origins, dirs
         rays["t_min"], rays["t_max"] = t_min, t_max
         return self.raycast_rays(rays, level)
+
+    def _shape_lib(self):
+        if not self._L.has_shapecast:
+            raise VoxelsHipError("%s has no sphere casts or closest points (vx_spherecast*, vx_closest_point*)" % self._L.path)
+        return self._L.lib
+
+    def spherecast_device(self, d_casts, n, d_hits, level=0):
+        """vx_spherecast_device: n casts at device address d_casts (SPHERE_CAST_DTYPE records, 16-byte aligned) -> d_hits
+        (SPHERE_HIT_DTYPE), queued on the context's stream."""
+        self._check(self._shape_lib().vx_spherecast_device(self._h, int(level), C.c_void_p(d_casts), int(n), C.c_void_p(d_hits)),
+                    "vx_spherecast_device")
+
+    def spherecast_casts(self, casts, level=0):
+        """vx_spherecast on a SPHERE_CAST_DTYPE array -> SPHERE_HIT_DTYPE array (synchronous)."""
+        casts = np.ascontiguousarray(casts, SPHERE_CAST_DTYPE)
+        hits = np.zeros(casts.size, SPHERE_HIT_DTYPE)
+        self._check(self._shape_lib().vx_spherecast(self._h, int(level), _ptr(casts) if casts.size else None, casts.size,
+                                                    _ptr(hits) if casts.size else None), "vx_spherecast")
+        return hits
+
+    def spherecast(self, origins, dirs, radius, t_min=0.0, t_max=float("inf"), level=0):
+        """First contact of a sphere of `radius` (a scalar or one per cast) whose centre moves along o + t d (t_min <= t <= t_max,
+        t in units of |d|) with the regular meshes of one level, in mesh space (Y-up, voxels): a SPHERE_HIT_DTYPE array (misses:
+        t = inf, entry = block_id = tri = RAY_NONE)."""
+        origins = np.asarray(origins, np.float32).reshape(-1, 3)
+        dirs = np.asarray(dirs, np.float32).reshape(-1, 3)
+        n = max(len(origins), len(dirs))
+        casts = np.zeros(n, SPHERE_CAST_DTYPE)
+        casts["origin"], casts["dir"] = origins, dirs
+        casts["t_min"], casts["t_max"], casts["radius"] = t_min, t_max, radius
+        return self.spherecast_casts(casts, level)
+
+    def closest_points_device(self, d_queries, n, d_hits, level=0):
+        """vx_closest_point_device: n queries at device address d_queries (POINT_QUERY_DTYPE, 16-byte aligned) -> d_hits
+        (POINT_HIT_DTYPE), queued on the context's stream."""
+        self._check(self._shape_lib().vx_closest_point_device(self._h, int(level), C.c_void_p(d_queries), int(n), C.c_void_p(d_hits)),
+                    "vx_closest_point_device")
+
+    def closest_points_queries(self, queries, level=0):
+        """vx_closest_point on a POINT_QUERY_DTYPE array -> POINT_HIT_DTYPE array (synchronous)."""
+        queries = np.ascontiguousarray(queries, POINT_QUERY_DTYPE)
+        hits = np.zeros(queries.size, POINT_HIT_DTYPE)
+        self._check(self._shape_lib().vx_closest_point(self._h, int(level), _ptr(queries) if queries.size else None, queries.size,
+                                                       _ptr(hits) if queries.size else None), "vx_closest_point")
+        return hits
+
+    def closest_points(self, points, max_dist=float("inf"), level=0):
+        """Nearest point of the regular meshes of one level to each point, if within max_dist (a scalar or one per point), in mesh
+        space: a POINT_HIT_DTYPE array (nothing within max_dist: dist = inf, entry = block_id = tri = RAY_NONE)."""
+        points = np.asarray(points, np.float32).reshape(-1, 3)
+        q = np.zeros(len(points), POINT_QUERY_DTYPE)
+        q["pos"], q["max_dist"] = points, max_dist
+        return self.closest_points_queries(q, level)
 
     def _lod_lib(self):
         if not self._L.has_lod:

@@ -4097,4 +4097,5 @@ struct Backend {
 
 #include "vx_host.inl"
 #include "vx_ray.inl"
+#include "vx_shape.inl"
 #include "vx_lod.inl"
