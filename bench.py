@@ -14,6 +14,11 @@ halo (1 distance layer down, 2 distance + 1 material + 1 blend layer up) is exch
 --halo-every-step, inside every step, as the path does after an edit.  Inputs are generated on the device
 (vx_grid_create_terrain / vx_grid_fill_terrain: the bytes of the host generator voxels_synth) and are resident in HBM
 before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set up, warm up, time the steps, write --dump-outputs, print the
+line.  Everything else - per-kernel stage times and the roofline, end-to-end and cold figures, the uncached, edit and
+'caves' workloads, the drop-in library's Execute, the CPU baseline with its parity check against the reference, and with
+N > 1 the other halo variant and the multi-GPU self-check - runs only with --full.
 """
 import argparse
 import json
@@ -35,6 +40,9 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--n", type=int, default=int(os.environ.get("VOXELS_BENCH_N", "1024")))
     ap.add_argument("--levels", type=int, default=int(os.environ.get("VOXELS_BENCH_LEVELS", "4")))
+    ap.add_argument("--full", action="store_true", help="after the headline, everything else the benchmark measures and checks (stage times, roofline, "
+                    "end-to-end, cold, uncached, edit and 'caves' figures, drop-in Execute, CPU baseline and parity vs the reference, N > 1: "
+                    "the other halo variant and the multi-GPU self-check); the --no-* options below trim it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--slab-axis", choices=["y", "z"], default="y", help="axis along which the grid is cut into one slab per GPU (y balances height-field terrains, whose surface sits in a few z-layers)")
     ap.add_argument("--serialize", action="store_true", help="run EVERY launch of this process with the library's streams serialised (one kernel at a time), for per-kernel profiling: the end-to-end figures are skipped")
@@ -372,6 +380,45 @@ def main():
     dumped = None
     if args.dump_outputs:
         dumped = dump_outputs(args.dump_outputs, poly.all_levels(), prefix="rank%d_" % rank if world > 1 else "", budget=DUMP_BUDGET // world)
+
+    # what the line says about the run in either mode; --full adds its own figures to it
+    base = {"workload": "%d^3 procedural noise terrain (seed %d), materials, LOD levels 0..%d with transition cells, "
+                        "%s-slab sharded over %d GPU(s)" % (n, seed, levels - 1, axis, world),
+            "grid": n, "levels": levels, "parallelism": "%sslab%d" % (axis, world),
+            "active_blocks": [int(x) for x in info.active_blocks[:levels]],
+            "device_gen_s": round(t_gen, 3),
+            "halo_exchange_in_step": bool(world > 1 and args.halo_every_step), "halo_transport": halo_transport, "c_abi_rccl_error": comm_error,
+            "step_definition": "r03+: one vx_polygonize per step on a resident grid; with N > 1 the slab halo is exchanged once before "
+                               "the steps (vx_halo_exchange) unless --halo-every-step (r01/r02 exchanged it inside every step: "
+                               "compare those rounds with ms_per_step_with_halo_exchange)",
+            "full": bool(args.full)}
+
+    def result_line(config):
+        step_s = elapsed / args.steps
+        return {
+            "metric": "Mvoxels/s polygonized (1024^3 grid, 4 LOD levels)" if (n == 1024 and levels == 4) else "Mvoxels/s polygonized (%d^3 grid, %d LOD levels)" % (n, levels),
+            "value": round(n ** 3 / step_s / 1e6, 2),
+            "unit": "Mvoxels/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "i8",
+            "data": "synthetic",
+            "dry_run": bool(dry),  # (true only for tests/test_bench_dry_run.py: the script's control flow on CPU, numbers meaningless)
+            "config": config,
+        }
+
+    if not args.full:
+        if rank == 0:
+            out = result_line(base)
+            if args.dump_outputs:
+                out["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
+            print(json.dumps(out))
+        if world > 1:
+            dist_pkg.destroy_process_group()
+        return
 
     # N > 1: the other variant as well - a step that includes the halo exchange (what a run after an edit pays) when the
     # timed steps above ran without it, and the other way round.  Every rank runs the same sequence (no collective is
@@ -795,36 +842,16 @@ def main():
 
     if rank == 0:
         step_s = elapsed / args.steps
-        out = {
-            "metric": "Mvoxels/s polygonized (1024^3 grid, 4 LOD levels)" if (n == 1024 and levels == 4) else "Mvoxels/s polygonized (%d^3 grid, %d LOD levels)" % (n, levels),
-            "value": round(n ** 3 / step_s / 1e6, 2),
-            "unit": "Mvoxels/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "i8",
-            "data": "synthetic",
-            "dry_run": bool(dry),  # (true only for tests/test_bench_dry_run.py: the script's control flow on CPU, numbers meaningless)
-            "config": {"workload": "%d^3 procedural noise terrain (seed %d), materials, LOD levels 0..%d with transition cells, "
-                                   "%s-slab sharded over %d GPU(s)" % (n, seed, levels - 1, axis, world),
-                       "grid": n, "levels": levels, "parallelism": "%sslab%d" % (axis, world),
-                       "active_blocks": [int(x) for x in info.active_blocks[:levels]],
-                       "verts": int(totals[0]), "indices": int(totals[1]), "tverts": int(totals[2]), "tindices": int(totals[3]),
-                       "surface_only": {"surface_blocks_per_s": round(surface_blocks / step_s, 1),
-                                        "Mvoxels_per_s_over_surface_blocks": round(surface_blocks * 4096 / step_s / 1e6, 2),
-                                        "note": "a height-field terrain keeps its surface in %d of %d level-0 blocks; `value` counts every voxel of the grid, as the metric defines it" % (surface_blocks, (n // 16) ** 2 * (planes // 16))},
-                       "stage_ms_serialized": stage_ms, "whole_execute": whole, "e2e_ms": e2e, "device_gen_s": round(t_gen, 3),
-                       "halo_exchange_in_step": bool(world > 1 and args.halo_every_step), "halo_transport": halo_transport, "c_abi_rccl_error": comm_error,
-                       "step_definition": "r03+: one vx_polygonize per step on a resident grid; with N > 1 the slab halo is exchanged once before "
-                                          "the steps (vx_halo_exchange) unless --halo-every-step (r01/r02 exchanged it inside every step: "
-                                          "compare those rounds with ms_per_step_with_halo_exchange)",
-                       "multi_gpu_check": (multi_gpu_check["result"] if multi_gpu_check else None), "multi_gpu_check_detail": multi_gpu_check,
-                       ("ms_per_step_without_halo_exchange" if args.halo_every_step else "ms_per_step_with_halo_exchange"): (round(ms_other, 4) if ms_other is not None else None),
-                       "cold": cold, "steady_state_uncached": uncached, "edit": edit},
-            "roofline": roofline,
-        }
+        out = result_line(dict(base, **{
+            "verts": int(totals[0]), "indices": int(totals[1]), "tverts": int(totals[2]), "tindices": int(totals[3]),
+            "surface_only": {"surface_blocks_per_s": round(surface_blocks / step_s, 1),
+                             "Mvoxels_per_s_over_surface_blocks": round(surface_blocks * 4096 / step_s / 1e6, 2),
+                             "note": "a height-field terrain keeps its surface in %d of %d level-0 blocks; `value` counts every voxel of the grid, as the metric defines it" % (surface_blocks, (n // 16) ** 2 * (planes // 16))},
+            "stage_ms_serialized": stage_ms, "whole_execute": whole, "e2e_ms": e2e,
+            "multi_gpu_check": (multi_gpu_check["result"] if multi_gpu_check else None), "multi_gpu_check_detail": multi_gpu_check,
+            ("ms_per_step_without_halo_exchange" if args.halo_every_step else "ms_per_step_with_halo_exchange"): (round(ms_other, 4) if ms_other is not None else None),
+            "cold": cold, "steady_state_uncached": uncached, "edit": edit}))
+        out["roofline"] = roofline
         if args.dump_outputs:
             out["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
         if world == 1 and not args.no_cpu_baseline and not args.serialize:

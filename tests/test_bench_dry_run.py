@@ -24,7 +24,7 @@ def test_bench_two_ranks_on_cpu(axis, port):
     path = build.build_emu()
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=port, WORLD_SIZE="2", OMP_NUM_THREADS="2", VOXELS_HIP_LIBRARY=path)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--n", "128", "--levels", "3",
-           "--slab-axis", axis, "--dry-run-cpu", "--no-cpu-baseline", "--no-extra", "--no-isolated"]
+           "--slab-axis", axis, "--dry-run-cpu", "--full", "--no-cpu-baseline", "--no-extra", "--no-isolated"]
     procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for r in range(2)]
     outs = [p.communicate(timeout=900) for p in procs]
     for r, (p, (so, se)) in enumerate(zip(procs, outs)):
@@ -111,7 +111,7 @@ def test_bench_dump_outputs_on_cpu(tmp_path):
     for run in range(2):
         d = str(tmp_path / ("run%d" % run))
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "0", "--n", "128", "--levels", "3",
-               "--dry-run-cpu", "--no-cpu-baseline", "--no-extra", "--no-isolated", "--dump-outputs", d]
+               "--dry-run-cpu", "--full", "--no-cpu-baseline", "--no-extra", "--no-isolated", "--dump-outputs", d]
         procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for r in range(2)]
         outs = [p.communicate(timeout=900) for p in procs]
         for r, (p, (so, se)) in enumerate(zip(procs, outs)):
@@ -132,3 +132,37 @@ def test_bench_dump_outputs_on_cpu(tmp_path):
     assert all(len(v) for v in dumps[0].values()), "every file written holds values"
     totals = line["config"]["multi_gpu_check_detail"]["totals_per_level_blocks_verts_indices_tverts_tindices"]
     assert (counts[0] + counts[1]).tolist() == [[float(x) for x in row] for row in totals[:len(counts[0])]]
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """A plain `bench.py` run (no --full) on one rank: it sets up, warms up, times the steps, writes --dump-outputs and prints
+    the line - with the headline's keys and none of the figures --full adds - and what it dumps is what the --full run of the
+    same arguments dumps."""
+    from voxels_amd import build
+    path = build.build_emu()
+    env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", OMP_NUM_THREADS="2", VOXELS_HIP_LIBRARY=path)
+    lines, dumps = {}, {}
+    for mode in ("plain", "full"):
+        d = str(tmp_path / mode)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--n", "128", "--levels", "3",
+               "--dry-run-cpu", "--no-cpu-baseline", "--no-extra", "--no-isolated", "--dump-outputs", d] + (["--full"] if mode == "full" else [])
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, "%s run failed:\n%s" % (mode, r.stderr[-3000:])
+        found = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(found) == 1, "ONE JSON line"
+        lines[mode] = json.loads(found[0])
+        dumps[mode] = {f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    plain, full = lines["plain"], lines["full"]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert key in plain, key
+    assert plain["metric"] == full["metric"] == "Mvoxels/s polygonized (128^3 grid, 3 LOD levels)"
+    assert plain["unit"] == "Mvoxels/s" and plain["higher_is_better"] is True and plain["dtype"] == "i8"
+    assert abs(plain["value"] - 128 ** 3 / (plain["ms_per_step"] * 1e-3) / 1e6) < 0.01 * plain["value"]
+    assert plain["steps"] == 2 and plain["warmup"] == 1 and plain["dump_outputs"]["dir"] == str(tmp_path / "plain")
+    assert plain["config"]["full"] is False and full["config"]["full"] is True
+    assert "roofline" not in plain and "cpu_baseline" not in plain and "parity_vs_reference" not in plain
+    for key in ("stage_ms_serialized", "whole_execute", "e2e_ms", "cold", "steady_state_uncached", "edit", "extra", "multi_gpu_check"):
+        assert key not in plain["config"], key
+    assert "roofline" in full and full["config"]["e2e_ms"] and full["config"]["cold"]
+    assert plain["config"]["active_blocks"] == full["config"]["active_blocks"]
+    assert dumps["plain"].keys() == dumps["full"].keys() and all(np.array_equal(dumps["plain"][f], dumps["full"][f]) for f in dumps["plain"])

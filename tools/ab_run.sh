@@ -9,7 +9,7 @@ for spec in "$@"; do
   name=${spec%%:*}; envs=""; [ "$spec" != "$name" ] && envs=$(echo "${spec#*:}" | tr ':' ' ')
   lib=tools/ab/$name.so; [ "$name" = base ] && lib=voxels_amd/csrc/libvoxels_hip.so
   tag=$(echo "$spec" | tr ':=' '__')
-  env $envs VOXELS_HIP_LIBRARY=$lib timeout 300 python bench.py --steps 8 --warmup 2 --no-extra --no-cpu-baseline --serialize > "$out/bench_$tag.json" 2> "$out/bench_$tag.err"
+  env $envs VOXELS_HIP_LIBRARY=$lib timeout 300 python bench.py --full --steps 8 --warmup 2 --no-extra --no-cpu-baseline --serialize > "$out/bench_$tag.json" 2> "$out/bench_$tag.err"
   python - "$out/bench_$tag.json" "$spec" <<'PY'
 import json, sys
 try:

@@ -37,7 +37,7 @@ def parse(path):
 def main():
     d, n, levels, gpus, label = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), sys.argv[5]
     target = sys.argv[6] if len(sys.argv) > 6 else "profiles/pmc_latest.json"
-    command = sys.argv[7] if len(sys.argv) > 7 else "python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra --no-isolated"
+    command = sys.argv[7] if len(sys.argv) > 7 else "python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extra --no-isolated"
     fetch, ex1 = parse(d + "/pass1.txt")
     write, ex2 = parse(d + "/pass2.txt")
     out = {"n": n, "levels": levels, "gpus": gpus,

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=$1; shift
 mkdir -p "$out"
-cmd=${PMC_CMD:-python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra --no-isolated}
+cmd=${PMC_CMD:-python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extra --no-isolated}
 i=0
 for c in "$@"; do
   i=$((i+1))

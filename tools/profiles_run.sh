@@ -9,7 +9,7 @@ out=${1:-gpurun_out/prof}
 mkdir -p $out
 python -c "from voxels_amd import Polygonizer; p = Polygonizer(); print('selftest', p.selftest().tolist())" > $out/selftest.txt 2>&1
 timeout 1200 python -m pytest tests -m gpu -q > $out/gputests.log 2>&1; echo "pytest rc $?" >> $out/gputests.log
-timeout 900 python bench.py > $out/bench_default.json 2> $out/bench_default.err
+timeout 900 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 timeout 600 bash tools/kstats.sh $out/ks "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" "SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT SQ_INSTS_SMEM" "SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU" > $out/ks.log 2>&1
 timeout 600 bash tools/pmc_run.sh $out/pmc "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" > $out/pmc.log 2>&1
 PMC_CMD="python tools/caves_run.py 1024 4 3" timeout 600 bash tools/pmc_run.sh $out/pmc_caves "FETCH_SIZE" "WRITE_SIZE" > $out/pmc_caves.log 2>&1
