@@ -11,14 +11,6 @@
 // one vertex and one lane = one triangle (three indices).  5 barriers.
 namespace {
 
-#if defined(VX_F0_PROFILE)
-// tools builds: where a level-0 block's time goes inside f0_walk (cycles / 64 as thread 0 sees them, summed over all blocks)
-__device__ unsigned long long g_f0prof[12];
-#define F0_TICK(i) do { const unsigned long long now_ = __builtin_readcyclecounter(); if (tid == 0) atomicAdd(&g_f0prof[i], (now_ - f0Tick) >> 6); f0Tick = now_; } while (0)
-#else
-#define F0_TICK(i) do { } while (0)
-#endif
-
 constexpr u32 F0_TAB_FIXED = TAB_F0_BYTES - TAB_F0_CASE;   // case rows | triangle rows | edge infos | direction masks
 constexpr u32 F0_TAB_LDS = F0_TAB_FIXED + 2048;            // + the per-case vertex rows widened to 8 bytes
 
@@ -85,7 +77,6 @@ __device__ __forceinline__ void f0_request(const GridView& g, const LevelDesc& L
 {
 	const int tid = f0_opaque_tid();
 	const int n = g.n, cnt = (int)L.cnt;
-	if (VX_ABL & 4096) { pf.d[0] = pf.d[1] = pf.m[0] = pf.m[1] = pf.b[0] = pf.b[1] = make_uint4(0x01010101u, 0x01010101u, 0x01010101u, 0x81818181u); pf.dl[0] = pf.dl[1] = pf.dr[0] = pf.dr[1] = pf.mf[0] = pf.mf[1] = pf.bf[0] = pf.bf[1] = 0x01010101u; pf.bits = 0; return; }
 	// every lane loads (indices clamped into range): a conditional load with a default value makes the compiler wait for
 	// the data right behind the load, and these requests must stay in flight
 	if (!SELF) pf.bits = L.ntBits[(size_t)b.slot * 128 + (tid & 127)];
@@ -230,12 +221,14 @@ __device__ __forceinline__ bool f0_next(const ExecParamsDev& p, const LevelDesc&
 
 // The blocks of one walk, software-pipelined: `cur` has its inputs requested, `nxt` is accepted and gets them requested while
 // `cur` writes its output.  Leaves the LDS state free behind a barrier-less tail (callers meet before they reuse it).
+// The parameters are kernel argument 0, read through kernarg_params(): every caller is a __global__ whose first parameter is
+// the unmodified ExecParamsDev.
 template <int CAP, bool REMAP, bool SELF = false>
-__device__ __forceinline__ void f0_walk(const ExecParamsDev& pIn, const F0Tables& T, Fast0State<CAP>& st, u32* wgStats, u32* zeroFlag, u32& parity,
+__device__ __forceinline__ void f0_walk(const F0Tables& T, Fast0State<CAP>& st, u32* wgStats, u32* zeroFlag, u32& parity,
                                         u32 total, u32 lo, u32 first, u32 stride, u32 limit, const int tid)
 {
 	typedef R0<CAP> K;
-#define F0_PARAMS() (void)pIn; const ExecParamsDev& p = kernarg_params(); const LevelDesc& L = p.levels[0]; const GridView& g = p.G.grid; (void)L; (void)g
+#define F0_PARAMS() const ExecParamsDev& p = kernarg_params(); const LevelDesc& L = p.levels[0]; const GridView& g = p.G.grid; (void)L; (void)g
 	F0_PARAMS();
 	u32 it = first;
 	R0Block cur, nxt;
@@ -245,27 +238,21 @@ __device__ __forceinline__ void f0_walk(const ExecParamsDev& pIn, const F0Tables
 	if (have) f0_request<SELF>(g, L, cur, pf);
 	it += stride;
 	bool haveNext = have && f0_next<CAP, REMAP, SELF>(p, L, total, lo, stride, limit, it, f0_peek<REMAP>(p, L, total, limit, it), nxt);
-#if defined(VX_F0_PROFILE)
-	unsigned long long f0Tick = __builtin_readcyclecounter();
-#endif
 	while (have) {
 		F0_PARAMS();
 		const u32 candIt = it + stride;
 		R0Candidate cand;
-		F0_TICK(0); // (between blocks: next-item bookkeeping)
 		__syncthreads(); // the previous block is done with the LDS state (and the tables are staged)
-		F0_TICK(1);
 		{
 			const u32 z = f0_deposit<SELF>(st, L, cur, pf);
 			if (__ballot(z != 0) && (tid & 63) == 0) zeroFlag[parity] = 1;
 			if (tid == 0) zeroFlag[parity ^ 1u] = 0; // last read behind the previous block's second barrier
 		}
 		__syncthreads();
-		F0_TICK(2); // deposit (waits for the prefetched loads) + barrier
 		const bool clean = r0_uniform(zeroFlag[parity]) == 0;
 		parity ^= 1u;
 		bool requested = false;
-		bool mine = !(VX_ABL & 65536); // (SELF: the block turns out to have geometry, and no more cells than this capacity class holds; tools: 65536 = stop behind the deposit)
+		bool mine = true; // (SELF: the block turns out to have geometry, and no more cells than this capacity class holds)
 		if (SELF && mine) {
 			f0_self_bits(st, L, cur, tid);
 			__syncthreads();
@@ -275,8 +262,7 @@ __device__ __forceinline__ void f0_walk(const ExecParamsDev& pIn, const F0Tables
 				if (cells == 0) reg_write_empty_record(L, cur.slot);
 				if (cells > (u32)LARGE_THRESHOLD) atomicAdd(p.G.largeBlocks, 1u); // (the host repeats the run with the upper classes)
 			}
-			mine = cells != 0 && cells <= (u32)CAP && !(VX_ABL & 131072); // (tools: 131072 = stop behind the own bitmap)
-			F0_TICK(3); // own bitmap + barrier
+			mine = cells != 0 && cells <= (u32)CAP;
 		}
 		if (mine && clean) {
 			// ---- popcount prefix of the bitmap (every wave computes all of it: no exchange), compact cell list ----------
@@ -307,8 +293,6 @@ __device__ __forceinline__ void f0_walk(const ExecParamsDev& pIn, const F0Tables
 				}
 			}
 			__syncthreads();
-			F0_TICK(4); // prefix + compact list + barrier
-			if (!(VX_ABL & 262144)) { // (tools: stop behind the compact list)
 
 			// ---- cells: wave w owns the compact cells [w * Q, w * Q + Q), Q a multiple of 64; local scan per wave -----------
 			const u32 nt = r0_uniform(st.wordPrefix[128]);
@@ -333,8 +317,6 @@ __device__ __forceinline__ void f0_walk(const ExecParamsDev& pIn, const F0Tables
 				if (lane == 0) st.waveTot[wave] = carry;
 			}
 			__syncthreads();
-			F0_TICK(5); // cells + barrier
-			if (!(VX_ABL & 524288)) { // (tools: stop behind the cells)
 			{
 				u32 waveBase = 0, tot = 0;
 #pragma unroll
@@ -348,8 +330,7 @@ __device__ __forceinline__ void f0_walk(const ExecParamsDev& pIn, const F0Tables
 				// last lane makes them: its wave owns the tail of the compact list and is the first to run out of cells.
 				if (tid == WG - 1) {
 					st.vTotal = vTotal; st.tTotal = tTotal;
-					if (VX_ABL & 32768) { st.vOff = (cur.slot * 701u) % (p.P.vertCap - 4096u); st.iOff = (cur.slot * 4001u) % (p.P.idxCap - 16384u); } // (tools: what the returning atomic costs)
-					else reserve_both(p.P.cursors, vTotal, tTotal * 3u, st.vOff, st.iOff);
+					reserve_both(p.P.cursors, vTotal, tTotal * 3u, st.vOff, st.iOff);
 				}
 				for (u32 k0 = kBeg; k0 < kEnd; k0 += 64u) {
 					const u32 k = k0 + lane;
@@ -361,7 +342,6 @@ __device__ __forceinline__ void f0_walk(const ExecParamsDev& pIn, const F0Tables
 				}
 			}
 			__syncthreads();
-			F0_TICK(6); // bases + reservation + descriptors + barrier
 
 			const u32 vTotalU = r0_uniform(st.vTotal), tTotalU = r0_uniform(st.tTotal);
 			const int ox = (int)(cur.bx * 16), oy = (int)(cur.by * 16), oz = (int)(cur.bz * 16);
@@ -383,12 +363,12 @@ __device__ __forceinline__ void f0_walk(const ExecParamsDev& pIn, const F0Tables
 					for (u32 base = 0; base < vEnd || base < tEnd; base += WG) {
 						if (!requested) { if (haveNext) f0_request<SELF>(g, L, nxt, pf); cand = f0_peek<REMAP>(p, L, total, limit, candIt); requested = true; }
 						const u32 j = base + (u32)tid;
-						if (j < vEnd && !(VX_ABL & 1)) {
+						if (j < vEnd) {
 							const u32 desc = st.vdesc[j], c = desc & 0xFFFu;
 							const u32 cellId = st.matId[(c >> 8) * F0_MPLANE + ((c >> 4) & 15u) * F0_MROW + (c & 15u)];
 							f0_vertex(st, T, desc, ox, oy, oz, K::lut_row_waterfall(p.G.lut, cellId), vOut + j);
 						}
-						if (j < tEnd && !(VX_ABL & 2)) {
+						if (j < tEnd) {
 							u32 ids[3];
 							f0_triangle(st, T, j, ids);
 							u32* o3 = iOut + j * 3u; // 12 bytes per lane, consecutive lanes consecutive triangles
@@ -397,7 +377,6 @@ __device__ __forceinline__ void f0_walk(const ExecParamsDev& pIn, const F0Tables
 					}
 				}
 			}
-			F0_TICK(7); // vertices + triangles (+ the next block's requests)
 			if (tid == 0) {
 				BlockRecord& r = L.records[cur.slot];
 				r.coordId = cur.coord;
@@ -410,8 +389,6 @@ __device__ __forceinline__ void f0_walk(const ExecParamsDev& pIn, const F0Tables
 				if (!room) atomicOr(&p.P.cursors[CUR_OVF], 1u);
 				wgStats[0] += nt;
 			}
-			F0_TICK(8); // record
-			} }
 		} else if (mine && tid == 0) {
 			// a zero sample: the general pass takes the block
 			p.G.slowItems[0][atomicAdd(&p.G.slowCount[0], 1u)] = cur.slot;
@@ -444,7 +421,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 	const F0Tables T = f0_stage_tables(tab, p.tables);
 
 	u32 parity = 0;
-	f0_walk<CAP, true>(p, T, st, wgStats, zeroFlag, parity, total, lo, blockIdx.x, gridDim.x, (total + 63u) & ~63u, tid);
+	f0_walk<CAP, true>(T, st, wgStats, zeroFlag, parity, total, lo, blockIdx.x, gridDim.x, (total + 63u) & ~63u, tid);
 	__syncthreads();
 	if (tid < 20 && wgStats[tid]) atomicAdd(&p.G.stats[tid], wgStats[tid]);
 }
@@ -472,7 +449,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 	const F0Tables T = f0_stage_tables(tab, p.tables);
 
 	u32 parity = 0;
-	f0_walk<CAP, false>(p, T, st, wgStats, zeroFlag, parity, total, lo, blockIdx.x, gridDim.x, total, tid);
+	f0_walk<CAP, false>(T, st, wgStats, zeroFlag, parity, total, lo, blockIdx.x, gridDim.x, total, tid);
 	__syncthreads();
 	if (tid < 20 && wgStats[tid]) atomicAdd(&p.G.stats[tid], wgStats[tid]);
 }

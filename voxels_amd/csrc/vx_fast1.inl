@@ -95,7 +95,6 @@ __device__ __forceinline__ void f1_block(const ExecParamsDev& p, const F0Tables&
 	bitsWord = TV_LOAD_THROUGH(&L.ntBits[(size_t)slot * 128 + (tid & 127)]);
 	c0 = load16_through(csrc, (u32)tid * 16u); c1 = load16_through(csrc, (u32)(tid + WG) * 16u);
 
-	TRACE_MARK(0);
 	// ---- stage: bitmap, material cache block, 17 x 17 rows of 17 lattice samples; any zero among them? -------------
 	{
 		u32 zero = 0;
@@ -118,10 +117,8 @@ __device__ __forceinline__ void f1_block(const ExecParamsDev& p, const F0Tables&
 		if (tid == 0) zeroFlag[parity ^ 1u] = 0; // last read behind the previous block's second barrier
 	}
 	__syncthreads();
-	TRACE_MARK(1);
 	const bool clean = r0_uniform(zeroFlag[parity]) == 0;
 	parity ^= 1u;
-	if (VX_ABL & 8192) return;
 	if (!clean) {
 		if (tid == 0) p.G.slowItems[1][atomicAdd(&p.G.slowCount[1], 1u)] = (level << 24) | slot;
 		return;
@@ -154,7 +151,6 @@ __device__ __forceinline__ void f1_block(const ExecParamsDev& p, const F0Tables&
 	}
 	__syncthreads();
 
-	TRACE_MARK(2);
 	// ---- cells: wave w owns the compact cells [w * Q, w * Q + Q), Q a multiple of 64; local scan per wave -----------
 	const u32 nt = r0_uniform(st.wordPrefix[128]);
 	const u32 Q = ((nt + WG - 1) / WG) * 64u;
@@ -177,7 +173,6 @@ __device__ __forceinline__ void f1_block(const ExecParamsDev& p, const F0Tables&
 		if (lane == 0) st.waveTot[wave] = carry;
 	}
 	__syncthreads();
-	TRACE_MARK(3);
 	{
 		u32 waveBase = 0, tot = 0;
 #pragma unroll
@@ -202,7 +197,6 @@ __device__ __forceinline__ void f1_block(const ExecParamsDev& p, const F0Tables&
 	}
 	__syncthreads();
 
-	TRACE_MARK(4);
 	const u32 vTotalU = r0_uniform(st.vTotal), tTotalU = r0_uniform(st.tTotal);
 	const bool room = r0_uniform(st.vOff) + vTotalU <= p.P.vertCap && r0_uniform(st.iOff) + tTotalU * 3u <= p.P.idxCap;
 	const int ox = (int)(bx * 16 * L.mult), oy = (int)(by * 16 * L.mult), oz = (int)(bz * 16 * L.mult);
@@ -221,12 +215,12 @@ __device__ __forceinline__ void f1_block(const ExecParamsDev& p, const F0Tables&
 			u32* iOut = p.P.idx + r0_uniform(st.iOff) + ct * 3u;
 			for (u32 base = 0; base < vEnd || base < tEnd; base += WG) {
 				const u32 j = base + (u32)tid;
-				if (j < vEnd && !(VX_ABL & 32)) {
+				if (j < vEnd) {
 					const u32 desc = st.vdesc[j];
 					const unsigned long long lut = K::lut_row_waterfall(p.G.lut, (u32)st.cacheId[desc & 0xFFFu]);
 					if (!f1_vertex(st, T, smp, L.cache + (size_t)slot * BLOCK_CELLS, desc, (int)level, ox, oy, oz, lut, vOut + j)) notInterior = 1;
 				}
-				if (j < tEnd && !(VX_ABL & 64)) {
+				if (j < tEnd) {
 					u32 ids[3];
 					f0_triangle(st, T, j, ids);
 					u32* o3 = iOut + j * 3u;
@@ -236,7 +230,6 @@ __device__ __forceinline__ void f1_block(const ExecParamsDev& p, const F0Tables&
 		}
 		if (__ballot(notInterior != 0) && lane == 0) st.suspect = 1;
 	}
-	TRACE_MARK(5);
 	__syncthreads();
 	if (tid == 0) {
 		if (st.suspect) {

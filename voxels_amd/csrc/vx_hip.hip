@@ -76,16 +76,15 @@ __device__ __forceinline__ const ExecParamsDev& kernarg_params()
 	return *(const ExecParamsDev*)kp;
 }
 
-// tools builds (tools/ab_build.py x=-DVX_ABL=<bits>): parts of the work switched off to see what they cost in time and
-// instructions (tools/exp/r06_ablate.sh); the results of such a build are wrong by construction.  0 in the product.
-#if !defined(VX_ABL)
-#define VX_ABL 0
-#endif
-
 constexpr int WG = 256;
 constexpr int REG_CAP_SMALL = LARGE_THRESHOLD; // LDS capacity class of the regular pass that covers ordinary surfaces
 constexpr int REG_CAP_MID = 1536;               // second class of the table-driven passes (dense surfaces: three workgroups per CU instead of one in the 4096-cell class)
 constexpr int REG_CAP_BIG = 4096;               // third class of the table-driven passes: every block (two workgroups per CU; round 4 left blocks beyond 1536 cells to the general pass at one workgroup per CU)
+// Waves per SIMD of k_regular's first class: the lockstep LOD chains of the vertex emission keep a batch of vertices in
+// registers; at 5 waves (96 registers) the pass spilled them to scratch — and produced wrong vertices now and then
+// (drop-in byte-dump test).
+constexpr int REG_WAVES = 4;
+constexpr int TR_WAVES = 5;                     // waves per SIMD of k_transition (96 registers; the WIDE variants run 3)
 
 // ------------------------------------------------------------------------------------------------------
 // workgroup helpers
@@ -173,17 +172,6 @@ __device__ __forceinline__ void publish_done_through(unsigned long long* flag, u
 
 enum { WAIT_SPINS = 1u << 17 }; // x ~1 us per poll: a tenth of a second, against runs of a millisecond
 
-#if defined(VX_MAIN_TRACE)
-// tools builds: a timeline of k_main's items (100 MHz clock) - per item {kind << 28 | level << 24 | slot, workgroup, ticket drawn,
-// started, last wait over, done}; printed by vx_polygonize after the run (small grids)
-__device__ unsigned long long g_mainTrace[18 * 8192];
-__device__ u32 g_mainTraceN;
-__device__ unsigned long long g_waitEnd[4096];
-__device__ unsigned long long g_marks[4096 * 12];
-#define TRACE_MARK(i) do { if (threadIdx.x == 0) g_marks[(blockIdx.x & 4095u) * 12u + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define TRACE_MARK(i) do { } while (0)
-#endif
 // one lane: poll until the word carries this run's tag; returns its payload (0 after giving up).  Once one wait has given
 // up every other one does so at its next look (the run is lost; it must end, not hang the device).
 __device__ __forceinline__ u32 wait_done(const unsigned long long* flag, u32 epoch, u32* giveUp)
@@ -193,9 +181,6 @@ __device__ __forceinline__ u32 wait_done(const unsigned long long* flag, u32 epo
 		const unsigned long long v = __hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
 #else
 		const unsigned long long v = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-#if defined(VX_MAIN_TRACE)
-		if ((u32)(v >> 32) == epoch) { g_waitEnd[blockIdx.x & 4095u] = __builtin_amdgcn_s_memrealtime(); return (u32)v; }
 #endif
 		if ((u32)(v >> 32) == epoch) return (u32)v;
 		if (spins > (u32)WAIT_SPINS || ((spins & 255u) == 255u && __hip_atomic_load(giveUp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) { atomicOr(giveUp, 1u); return 0u; }
@@ -1249,15 +1234,8 @@ __global__ __launch_bounds__(WG) void k_classify(ExecParamsDev p, u32 rowGroup, 
 		if (bx < L.cnt) myClass = p.G.blockClass[block_coord_id(bx, by, bz, L.cnt)];
 		if (__ballot(!(myClass & BC_QUIET)) == 0ull) return; // (every wave holds the 16 classes four times over: uniform over the workgroup)
 	}
-#if defined(VX_CLS_PROFILE)
-	unsigned long long clsTick = __builtin_readcyclecounter();
-#define CLS_TICK(i) do { const unsigned long long now_ = __builtin_readcyclecounter(); if (tid == 0) atomicAdd(&p.G.largeBlocks[16 + (i)], (u32)((now_ - clsTick) >> 4)); clsTick = now_; } while (0)
-#else
-#define CLS_TICK(i) do { } while (0)
-#endif
 	if (tid < TB) { blockAny[tid] = 0; blockCnt[tid] = 0; blockSlot[tid] = -1; blockCls[tid] = myClass; }
 	__syncthreads();
-	CLS_TICK(0);
 
 	// ---- load from the brick mirror: the TB blocks of a tile are 64 KB of consecutive addresses, lane t takes the 16-byte
 	//      voxel row t (memory order) of every block, so a wave reads 1 KB at a stretch (the dense field would hand out the
@@ -1333,7 +1311,6 @@ __global__ __launch_bounds__(WG) void k_classify(ExecParamsDev p, u32 rowGroup, 
 		for (int i = 0; i < 2; ++i) { const int r = tid + i * WG; if (r < 289) halo[r] = (u8)((u32)(xv[i] >> 7) & 1u); }
 	}
 	__syncthreads();
-	CLS_TICK(1);
 
 	// ---- classify the 16*TB cells of one (y,z) row per thread, bit-parallel -----------------------------
 	{
@@ -1373,7 +1350,6 @@ __global__ __launch_bounds__(WG) void k_classify(ExecParamsDev p, u32 rowGroup, 
 		}
 	}
 	__syncthreads();
-	CLS_TICK(2);
 
 	// ---- one lane per block: emptiness rule, slot allocation (one reservation per tile) -------------------
 	if (tid < 64) { // the first wave; lanes >= TB only take part in the ballots
@@ -1428,7 +1404,6 @@ __global__ __launch_bounds__(WG) void k_classify(ExecParamsDev p, u32 rowGroup, 
 		}
 	}
 	__syncthreads();
-	CLS_TICK(3);
 #pragma unroll
 	for (int j = 0; j < TB; ++j) {
 		const int slot = blockSlot[j];
@@ -1438,7 +1413,6 @@ __global__ __launch_bounds__(WG) void k_classify(ExecParamsDev p, u32 rowGroup, 
 			((u16*)(L.consBits + (size_t)slot * 128))[tid] = blockSkipped[j] ? (u16)0 : bits;
 		}
 	}
-	CLS_TICK(4);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1558,7 +1532,6 @@ __device__ __forceinline__ void mat_block(const ExecParamsDev& p, u32 level, u32
 	const bool defineAll = !p.G.dirty || slot >= p.G.prevActive[level];
 	u16* cacheOut = L.cache + (size_t)slot * BLOCK_CELLS;
 	__syncthreads(); // the previous block of this workgroup is done with the LDS state
-	TRACE_MARK(0);
 
 	// ---- requests: child slots, old cache contents (incremental runs), samples ----------------------
 	int cs = -1;
@@ -1582,7 +1555,6 @@ __device__ __forceinline__ void mat_block(const ExecParamsDev& p, u32 level, u32
 	}
 	((uint4*)st.out)[tid] = old0; ((uint4*)st.out)[tid + WG] = old1;
 	__syncthreads();
-	TRACE_MARK(1);
 	if (lattice) {
 		// the level's lattice copy (complete: it is kept with the grid's mirrors): one 16-byte load + one byte per sample row
 		for (int r = tid; r < 289; r += WG) {
@@ -1610,7 +1582,6 @@ __device__ __forceinline__ void mat_block(const ExecParamsDev& p, u32 level, u32
 			if (sIdx < SAMPLES) atomicOr(&st.rowMask[sIdx / 17], (((u32)(v[q] >> 7)) & 1u) << (sIdx % 17));
 		}
 	}
-	TRACE_MARK(2);
 	// ---- child bitmaps (level 1) requested while the rows are classified -----------------------------
 	u32 cb4[4] = { 0, 0, 0, 0 };
 	if (level == 1 && selfChild) {
@@ -1693,7 +1664,6 @@ __device__ __forceinline__ void mat_block(const ExecParamsDev& p, u32 level, u32
 		}
 	}
 	__syncthreads();
-	TRACE_MARK(3);
 	const int y = tid & 15, z = tid >> 4;
 	u32 nt;
 	{
@@ -1732,7 +1702,6 @@ __device__ __forceinline__ void mat_block(const ExecParamsDev& p, u32 level, u32
 		for (int q = 0; q < 4; ++q) { const int w = tid + q * WG; st.childBits[w >> 7][w & 127] = cb4[q]; }
 	}
 	__syncthreads();
-	TRACE_MARK(4);
 	if (PARTIAL && level == 1u && selfChild) {
 		// (what f0_self_bits / f0_next<SELF> leave behind a level-0 block: here for all eight children at once)
 #pragma unroll
@@ -1811,7 +1780,6 @@ __device__ __forceinline__ void mat_block(const ExecParamsDev& p, u32 level, u32
 		}
 	}
 	__syncthreads();
-	TRACE_MARK(5);
 	if (GATED && level >= 2u) {
 		// the children's cache blocks are written by other workgroups of this launch (the level below comes first in the queue)
 		if (tid < 8) {
@@ -1825,13 +1793,12 @@ __device__ __forceinline__ void mat_block(const ExecParamsDev& p, u32 level, u32
 		}
 		acquire_and_meet(tid < 64);
 	}
-	TRACE_MARK(6);
 	// ---- vote.  A lane takes VB cells per trip and requests ALL their child entries before it looks at any: children
 	//      that are neighbours along x come in one load (two u16 entries / two material bytes), and no load is
 	//      conditional (a load with a default value is waited for on the spot) — the children of a cell are always
 	//      inside the grid; entries the consistency bits rule out are masked after the fact. ----------------------------
 	{
-		const int nVote = (VX_ABL & 16) ? 0 : (int)st.voteCount;
+		const int nVote = (int)st.voteCount;
 		// the children's materials come from the brick mirrors: the 2 x 2 x 2 child blocks are 8 consecutive-in-x pairs of
 		// 4 KB bricks, a cell's 8 children sit in 2 lines per field (4 in the dense fields)
 		const size_t childOrigin = brick_base(g, (int)(bx * 2), (int)(by * 2), (int)(bz * 2));
@@ -1901,7 +1868,6 @@ __device__ __forceinline__ void mat_block(const ExecParamsDev& p, u32 level, u32
 		}
 	}
 	__syncthreads();
-	TRACE_MARK(7);
 	if (THROUGH) {
 		store16_through(cacheOut, (u32)tid * 16u, ((const uint4*)st.out)[tid]);
 		store16_through(cacheOut, (u32)(tid + WG) * 16u, ((const uint4*)st.out)[tid + WG]);
@@ -1986,11 +1952,6 @@ __device__ __forceinline__ Tables stage_transition_tables(u8* lds, const u8* ima
 namespace {
 
 // One capacity class of the regular pass of levels >= 1: blocks with lo < non-trivial cells <= CAP
-// 4 waves per SIMD: the lockstep LOD chains of the vertex emission keep a batch of vertices in registers; at 5 waves (96
-// registers) the pass spilled them to scratch — and produced wrong vertices now and then (drop-in byte-dump test)
-#if !defined(VX_REG_WAVES)
-#define VX_REG_WAVES 4
-#endif
 // MODE 0: the slots of the levels [levelBegin, levels) (or the work lists of an incremental run); MODE 2: the blocks the
 // fast pass of the levels >= 1 (vx_fast1.inl) handed on (Globals::slowItems[1])
 // (the pass as workgroup `first` of `stride`: a launch of its own - k_regular below - or the second group of workgroups of
@@ -2018,13 +1979,6 @@ __device__ __forceinline__ bool regular_pass(const ExecParamsDev& p, u32 levelBe
 	if (first >= ((total + 63u) & ~63u)) return false; // the grid is sized before the block counts are known
 	const Tables T = stage_regular_tables(tab, p.tables); // visible after the first barrier of the item loop
 	const int tid = threadIdx.x;
-#if defined(VX_REG_PROFILE)
-	u32 prof[16] = { 0 };
-	unsigned long long tick = __builtin_readcyclecounter();
-#define RG_TICK(i) do { const unsigned long long now_ = __builtin_readcyclecounter(); prof[i] += (u32)(now_ - tick); tick = now_; } while (0)
-#else
-#define RG_TICK(i) do { } while (0)
-#endif
 
 	for (u32 it = first; it < ((total + 63u) & ~63u); it += stride) {
 		const u32 item = xcd_item(it);
@@ -2046,13 +2000,10 @@ __device__ __forceinline__ bool regular_pass(const ExecParamsDev& p, u32 levelBe
 			if (tid == 0) reg_write_empty_record(L, b.slot);
 			continue;
 		}
-		RG_TICK(0);
 		__syncthreads();
-		RG_TICK(1);
 		reg_phase_begin(st, L, b.slot, tid, WG);
 		gpu_reg_stage(p.G, b, st.samp);
 		__syncthreads();
-		RG_TICK(2);
 		for (int w = tid; w < 128; w += WG) st.wordPrefix[w] = (u16)__popc(st.ntBits[w]);
 		__syncthreads();
 		{
@@ -2060,62 +2011,46 @@ __device__ __forceinline__ bool regular_pass(const ExecParamsDev& p, u32 levelBe
 			if (tid == 0) st.wordPrefix[128] = (u16)nt;
 		}
 		__syncthreads();
-		RG_TICK(3);
 		reg_phase_list(st, L, b, tid, WG);
 		__syncthreads();
-		RG_TICK(4);
 		reg_phase_cells(st, T, p.G, L, b, tid, WG);
 		__syncthreads();
-		RG_TICK(5);
 		reg_phase_count(st, T, b, tid, WG);
 		__syncthreads();
-		RG_TICK(6);
 		{
 			const u32 vt = block_exclusive_scan_u16(st.vbase, st.wordPrefix[128], scanScratch);
 			if (tid == 0) { st.vTotal = vt; st.vOff = atomicAdd(&p.P.cursors[CUR_V], vt); }
 		}
 		__syncthreads();
-		RG_TICK(7);
 		for (u32 chunk = 0; chunk == 0 || chunk < st.vTotal; chunk += VDESC_CAP) {
 			if (chunk) __syncthreads();
 			reg_phase_describe(st, chunk, tid, WG);
 			__syncthreads();
-			RG_TICK(8);
 			reg_phase_emit_vertices(st, T, p.G, p.P, b, chunk, tid, WG);
-			RG_TICK(9);
 		}
 		__syncthreads();
-		RG_TICK(10);
 		reg_phase_keep(st, T, p.G, b, tid, WG);
 		__syncthreads();
-		RG_TICK(11);
 		{
 			const u32 it = block_exclusive_scan_u16(st.ibase, st.wordPrefix[128], scanScratch);
 			if (tid == 0) { st.iTotal = it; st.iOff = atomicAdd(&p.P.cursors[CUR_I], it); }
 		}
 		__syncthreads();
-		RG_TICK(12);
 		for (u32 chunk = 0; chunk < st.iTotal; chunk += VDESC_CAP) {
 			if (chunk) __syncthreads();
 			reg_phase_stage_indices(st, T, chunk, tid, WG);
 			__syncthreads();
-			RG_TICK(13);
 			reg_phase_flush_indices(st, T, p.P, chunk, tid, WG);
-			RG_TICK(14);
 		}
 		reg_phase_record(st, wgStats, L, b, p.P, tid);
-		RG_TICK(15);
 	}
-#if defined(VX_REG_PROFILE)
-	if (tid == 0 && !lo) for (int i = 0; i < 16; ++i) if (prof[i]) atomicAdd(&p.G.largeBlocks[16 + i], prof[i] >> 10); // header words 192..207, units of 1024 cycles
-#endif
 	__syncthreads();
 	if (threadIdx.x < 20 && wgStats[threadIdx.x]) atomicAdd(&p.G.stats[threadIdx.x], wgStats[threadIdx.x]);
 	return true;
 }
 
 template <int CAP, int MODE>
-__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(CAP > REG_CAP_SMALL ? 1 : VX_REG_WAVES))) void k_regular(ExecParamsDev p, u32 levelBegin, u32 levels, u32 lo)
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(CAP > REG_CAP_SMALL ? 1 : REG_WAVES))) void k_regular(ExecParamsDev p, u32 levelBegin, u32 levels, u32 lo)
 {
 	(void)regular_pass<CAP, MODE>(p, levelBegin, levels, lo, blockIdx.x, gridDim.x);
 }
@@ -2270,9 +2205,6 @@ __device__ __forceinline__ void tr_planes_store(const uint4& r0, const uint4& r1
 	}
 }
 
-#if !defined(VX_TR_WAVES)
-#define VX_TR_WAVES 5
-#endif
 // WIDE: a brick mirror of 4 GiB or more (grids beyond 1024^3): 64-bit voxel offsets around the vertices
 // (three waves per SIMD there: the 64-bit address terms do not fit the 128 registers of four)
 // One block of a level with transition cells.  GATED (k_main): the block's material cache comes from another workgroup of the
@@ -2287,17 +2219,9 @@ __device__ __forceinline__ void tr_block(const ExecParamsDev& p, RegBlockCtx b, 
 	// saved here.)
 	bool matReady = !GATED || matKnown;
 	const bool preMat = matReady;
-#if defined(VX_TR_PROFILE)
-	// tools builds: where a transition block's time goes (cycles / 64 as thread 0 sees them; header words 192..)
-	unsigned long long trTick = __builtin_readcyclecounter();
-#define TRB_TICK(i) do { const unsigned long long now_ = __builtin_readcyclecounter(); if (tid == 0) atomicAdd(&p.G.largeBlocks[16 + (i)], (u32)((now_ - trTick) >> 6)); trTick = now_; } while (0)
-#else
-#define TRB_TICK(i) do { } while (0)
-#endif
 	const LevelDesc& L = p.levels[b.level];
 	b.mult = L.mult;
 	block_coords(__builtin_amdgcn_readfirstlane(coordId), L.cnt, b.bx, b.by, b.bz);
-	
 
 	{
 		u32 on = 0;
@@ -2326,7 +2250,6 @@ __device__ __forceinline__ void tr_block(const ExecParamsDev& p, RegBlockCtx b, 
 				fm[f] = TV_LOAD_THROUGH(&cache[(u32)((local[2] << 8) | (local[1] << 4) | local[0])]);
 			}
 		}
-		TRB_TICK(0);
 		
 		// A boundary plane whose samples all have one sign holds no transition cell.  The sign summaries of the level-0
 		// blocks (MirrorState::blockSign: "every voxel of the block's plane x = 0 / y = 0 / z = 0 is >= 0 / < 0") decide
@@ -2363,7 +2286,6 @@ __device__ __forceinline__ void tr_block(const ExecParamsDev& p, RegBlockCtx b, 
 			if ((tid & 63) == 0 && quiet) atomicOr(&quietFaces[quietParity], quiet);
 		}
 		__syncthreads();
-		TRB_TICK(1);
 		on &= ~quietFaces[quietParity];
 		if (tid == 0) quietFaces[quietParity ^ 1u] = 0; // the other word is next written behind this barrier and read behind the next item's
 		quietParity ^= 1u;
@@ -2395,11 +2317,8 @@ __device__ __forceinline__ void tr_block(const ExecParamsDev& p, RegBlockCtx b, 
 		}
 	}
 	__syncthreads();
-	TRB_TICK(2);
 	tr_phase_classify(st, tid, WG);
 	__syncthreads();
-	if (VX_ABL & 2048) { for (int w = tid; w < 48; w += WG) st.ntAll[w] = 0; __syncthreads(); }
-	TRB_TICK(3);
 	for (int f0 = 0; f0 < 6;) {
 		const int f1 = tr_batch_end(st, f0); // uniform
 		__syncthreads();
@@ -2411,7 +2330,6 @@ __device__ __forceinline__ void tr_block(const ExecParamsDev& p, RegBlockCtx b, 
 			if (tid == 0) st.wordPrefix[48] = (u16)nt;
 		}
 		__syncthreads();
-		TRB_TICK(4);
 		if (st.wordPrefix[48] != 0) {
 			tr_phase_cells_of(st, tid, WG); // (the compact list needs no material: formed in front of the wait, one barrier for both)
 			if (GATED && !matReady) {
@@ -2421,13 +2339,10 @@ __device__ __forceinline__ void tr_block(const ExecParamsDev& p, RegBlockCtx b, 
 				matReady = true;
 			} else
 				__syncthreads();
-			TRB_TICK(5);
 			tr_phase_list(st, T, L, b, tid, WG, preMat ? st.faceMat : nullptr);
 			__syncthreads();
-			TRB_TICK(6);
 			tr_phase_count(st, T, tid, WG);
 			__syncthreads();
-			TRB_TICK(7);
 			{
 				// the reservation is requested here and first looked at behind the descriptors of the first chunk (which need
 				// none of it): one round trip off the block's chain
@@ -2442,24 +2357,21 @@ __device__ __forceinline__ void tr_block(const ExecParamsDev& p, RegBlockCtx b, 
 				if (tid == 0) { st.vOff = resV; st.iOff = resI; }
 			}
 			__syncthreads();
-			TRB_TICK(8);
 			for (u32 chunk = 0; chunk == 0 || chunk < st.vTotal; chunk += VDESC_CAP) {
 				if (chunk) {
 					__syncthreads();
 					tr_phase_describe(st, chunk, tid, WG);
 					__syncthreads();
 				}
-				if (!(VX_ABL & 512)) tr_phase_emit_vertices(st, T, p.G, smp, p.P, b, chunk, tid, WG);
+				tr_phase_emit_vertices(st, T, p.G, smp, p.P, b, chunk, tid, WG);
 			}
-			TRB_TICK(9);
-			for (u32 chunk = 0; chunk < ((VX_ABL & 1024) ? 0u : st.iTotal); chunk += TR_INDEX_CHUNK) {
+			for (u32 chunk = 0; chunk < st.iTotal; chunk += TR_INDEX_CHUNK) {
 				__syncthreads();
 				tr_phase_stage_indices(st, T, chunk, tid, WG);
 				__syncthreads();
 				tr_phase_flush_indices(st, T, p.P, chunk, tid, WG);
 			}
 		}
-		TRB_TICK(10);
 		tr_phase_record(st, L, b, p.P, f0, f1, tid);
 		f0 = f1;
 	}
@@ -2467,7 +2379,7 @@ __device__ __forceinline__ void tr_block(const ExecParamsDev& p, RegBlockCtx b, 
 }
 
 template <bool WIDE>
-__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WIDE ? 3 : VX_TR_WAVES))) void k_transition(ExecParamsDev p, u32 levels)
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WIDE ? 3 : TR_WAVES))) void k_transition(ExecParamsDev p, u32 levels)
 {
 	u8* tab = smem;
 	TrState& st = *(TrState*)(smem + TR_TAB_LDS);
@@ -3162,8 +3074,7 @@ struct Backend {
 	bool overlappedTail = false;                     // inside run_overlapped_tail
 	hipEvent_t evClassified = nullptr, evMaterial = nullptr, evSideA = nullptr, evSideB = nullptr, evMain = nullptr;
 	hipStream_t mainKeep = nullptr; // set while the tail of an overlapped run is queued on side stream A
-	hipStream_t copyStream[4] = { nullptr, nullptr, nullptr, nullptr }; // d2h_bulk
-	hipEvent_t evCopy = nullptr;
+	hipStream_t sideCopy = nullptr; // d2h_side
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
 	hipEvent_t evPrevEnd = nullptr; // the end of the previous timed run (idle_before_ms: diagnostics, VX_HOST_TIMING)
 	bool havePrevEnd = false;
@@ -3275,8 +3186,7 @@ struct Backend {
 		if (ev1) (void)hipEventDestroy(ev1);
 		if (evPrevEnd) (void)hipEventDestroy(evPrevEnd);
 		for (int i = 0; i < 9; ++i) if (stageEv[i]) (void)hipEventDestroy(stageEv[i]);
-		for (hipStream_t& cs : copyStream) if (cs) { (void)hipStreamDestroy(cs); cs = nullptr; }
-		if (evCopy) (void)hipEventDestroy(evCopy);
+		if (sideCopy) (void)hipStreamDestroy(sideCopy);
 		if (sideA) (void)hipStreamDestroy(sideA);
 		if (sideB) (void)hipStreamDestroy(sideB);
 		if (sideC) (void)hipStreamDestroy(sideC);
@@ -3346,8 +3256,8 @@ struct Backend {
 	bool d2h_side(void* d, const void* s, size_t bytes)
 	{
 		(void)hipSetDevice(device);
-		if (!copyStream[0] && hipStreamCreateWithFlags(&copyStream[0], hipStreamNonBlocking) != hipSuccess) return false;
-		return hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToHost, copyStream[0]) == hipSuccess && hipStreamSynchronize(copyStream[0]) == hipSuccess;
+		if (!sideCopy && hipStreamCreateWithFlags(&sideCopy, hipStreamNonBlocking) != hipSuccess) return false;
+		return hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToHost, sideCopy) == hipSuccess && hipStreamSynchronize(sideCopy) == hipSuccess;
 	}
 	void* alloc_pinned(size_t bytes)
 	{
@@ -3357,36 +3267,16 @@ struct Backend {
 	}
 	void free_pinned(void* p) { if (p) (void)hipHostFree(p); }
 	static void release_pinned(void* p) { if (p) (void)hipHostFree(p); } // arenas outlive their context
-	// Large device -> page-locked host copies, after everything queued on the run's stream: cut into pieces that
-	// can alternate between copy streams (VX_D2H_STREAMS > 1).  Measured on MI355X (tools/d2h_time.py, 499 MB): one stream
-	// 57 GB/s, 2-4 streams 53-56 GB/s - the link is the limit, so one stream is the default.
+	// Large device -> page-locked host copies on the run's stream, after everything queued there.  One stream: more copy
+	// streams bought nothing, one engine saturates the link (profiles/r03_d2h_time.txt).
 	bool d2h_bulk(void* const* dst, const void* const* src, const size_t* bytes, int count)
 	{
-		const u32 lanes = 1; // (more copy streams were measured and bought nothing: one engine saturates the link, profiles/r03_d2h_time.txt)
-		const size_t piece = (size_t)32 << 20;
 		size_t total = 0;
 		for (int i = 0; i < count; ++i) total += bytes[i];
 		if (!total) return true;
-		if (lanes == 1 || total <= piece) {
-			for (int i = 0; i < count; ++i)
-				if (bytes[i] && !check(hipMemcpyAsync(dst[i], src[i], bytes[i], hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(D2H)")) return false;
-			return check(hipStreamSynchronize(stream), "hipStreamSynchronize");
-		}
-		for (u32 l = 0; l < lanes; ++l)
-			if (!copyStream[l] && !check(hipStreamCreateWithFlags(&copyStream[l], hipStreamNonBlocking), "hipStreamCreate(copy)")) return false;
-		if (!evCopy && !check(hipEventCreateWithFlags(&evCopy, hipEventDisableTiming), "hipEventCreate(copy)")) return false;
-		if (!check(hipEventRecord(evCopy, stream), "hipEventRecord(copy)")) return false;
-		for (u32 l = 0; l < lanes; ++l) if (!check(hipStreamWaitEvent(copyStream[l], evCopy, 0), "hipStreamWaitEvent(copy)")) return false;
-		u32 next = 0;
-		bool ok = true;
-		for (int i = 0; i < count && ok; ++i)
-			for (size_t off = 0; off < bytes[i] && ok; off += piece) {
-				const size_t len = std::min(piece, bytes[i] - off);
-				ok = check(hipMemcpyAsync((char*)dst[i] + off, (const char*)src[i] + off, len, hipMemcpyDeviceToHost, copyStream[next]), "hipMemcpyAsync(D2H)");
-				next = (next + 1) % lanes;
-			}
-		for (u32 l = 0; l < lanes; ++l) ok = check(hipStreamSynchronize(copyStream[l]), "hipStreamSynchronize(copy)") && ok;
-		return ok;
+		for (int i = 0; i < count; ++i)
+			if (bytes[i] && !check(hipMemcpyAsync(dst[i], src[i], bytes[i], hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(D2H)")) return false;
+		return check(hipStreamSynchronize(stream), "hipStreamSynchronize");
 	}
 	void stage_enable(bool on)
 	{

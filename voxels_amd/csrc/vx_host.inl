@@ -46,7 +46,7 @@ typedef ListedBlock EmittedBlock;
 
 // largest grid edge: 2048 = 8 LOD levels (MAX_LEVELS) and 32-bit element offsets inside a block neighbourhood
 enum { VX_MAX_GRID = 2048 };
-enum { HDR_WORDS = 576, HDR_LISTS = 8, HDR_CURSORS = 32, HDR_STATS = 128, HDR_WORK = 160, HDR_LARGE = 176, HDR_SLOW = 224, HDR_UPPER = 256, HDR_GIVEUP = 288, HDR_PUBLISHED = 289 /* workgroups of the list pass that are done */, HDR_L0HEAD = 320 /* eight heads, one line each: k_main's level-0 queue per XCD */, HDR_PARTIALS = 32768 }; // counters spread over 128-byte lines
+enum { HDR_WORDS = 576, HDR_LISTS = 8, HDR_CURSORS = 32, HDR_STATS = 128, HDR_WORK = 160, HDR_LARGE = 176, HDR_SLOW = 224, HDR_UPPER = 256, HDR_GIVEUP = 288, HDR_PUBLISHED = 289 /* workgroups of the list pass that are done */, HDR_L0HEAD = 320 /* the head of k_main's level-0 queue, one for the chip */, HDR_PARTIALS = 32768 }; // counters spread over 128-byte lines
 
 } // namespace
 
@@ -1210,9 +1210,6 @@ GridView halo_view(const vx_ctx* c)
 // resident since round 4 (rebrick_row), so they have to follow the rows.  Two block layers: ~20 us at 1024^3.
 void refresh_halo_layers(vx_ctx* c)
 {
-#if defined(VX_NO_HALO_REFRESH) // (tools builds: shows that tests/test_gpu_parity.py::test_hip_halo_exchange_after_a_neighbour_changed needs it)
-	return;
-#endif
 	if (!c->be.wants_bricks() || c->bricksStale || !c->dBrick[0] || c->slabAxis == 0) return;
 	int dr[4], mr[4];
 	resident_ranges(c, dr, mr);
@@ -1590,80 +1587,6 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 		blocksCalculated += owned;
 		trivial += BLOCK_CELLS * (L == 0 ? c->hdr[HDR_STATS + 2] : owned);
 	}
-#if defined(VX_MAIN_PROFILE)
-	{
-		static const char* names[8] = { "barrier before dequeue", "dequeue", "level-0 batch", "material block", "regular block (levels >= 1)", "transition block", "exit", "-" };
-		unsigned long long sum = 0;
-		for (int i = 0; i < 8; ++i) sum += c->hdr[HDR_LARGE + 4 + i];
-		for (int i = 0; i < 7; ++i) fprintf(stderr, "[main profile] %-28s %10u x64 cycles  %5.1f %%\n", names[i], c->hdr[HDR_LARGE + 4 + i], 100.0 * c->hdr[HDR_LARGE + 4 + i] / (double)(sum ? sum : 1));
-	}
-#endif
-#if defined(VX_MAIN_TRACE)
-	{
-		u32 cnt = 0;
-		if (hipMemcpyFromSymbol(&cnt, HIP_SYMBOL(g_mainTraceN), sizeof(cnt)) == hipSuccess && cnt && cnt <= 4096u) {
-			std::vector<unsigned long long> v((size_t)cnt * 18);
-			if (hipMemcpyFromSymbol(v.data(), HIP_SYMBOL(g_mainTrace), v.size() * 8) == hipSuccess) {
-				unsigned long long t0 = ~0ull;
-				for (u32 i = 0; i < cnt; ++i) t0 = std::min(t0, v[18 * i + 2]);
-				static const char* kinds[4] = { "level0", "mat", "reg", "tr" };
-				for (u32 i = 0; i < cnt; ++i) {
-					const unsigned long long* e = &v[18 * i];
-					const u32 what = (u32)e[0];
-					fprintf(stderr, "[main trace] %-6s L%u slot %5u wg %4u  ticket %7.2f  start %7.2f  waited %7.2f  end %7.2f us\n", kinds[what >> 28], (what >> 24) & 15u, what & 0xFFFFFFu, (u32)e[1],
-					        (e[2] - t0) * 0.01, (e[3] - t0) * 0.01, e[4] ? (double)(long long)(e[4] - t0) * 0.01 : 0.0, (e[5] - t0) * 0.01);
-					if ((what >> 28) >= 1u) { fprintf(stderr, "             marks:"); for (int m = 0; m < 12; ++m) if (e[6 + m]) fprintf(stderr, " %d:%.2f", m, (double)(long long)(e[6 + m] - t0) * 0.01); fprintf(stderr, "\n"); }
-				}
-			}
-		}
-		cnt = 0;
-		(void)hipMemcpyToSymbol(HIP_SYMBOL(g_mainTraceN), &cnt, sizeof(cnt));
-	}
-#endif
-#if defined(VX_F0_PROFILE)
-	{
-		static const char* names[9] = { "between blocks", "top barrier", "deposit + barrier", "own bitmap + barrier", "prefix + list + barrier", "cells + barrier", "bases + reserve + describe + barrier", "vertices + triangles", "record" };
-		unsigned long long v[12], sum = 0;
-		if (hipMemcpyFromSymbol(v, HIP_SYMBOL(g_f0prof), sizeof(v)) == hipSuccess) {
-			for (int i = 0; i < 9; ++i) sum += v[i];
-			for (int i = 0; i < 9; ++i) fprintf(stderr, "[f0 profile] %-36s %12llu x64 cycles  %5.1f %%\n", names[i], v[i], 100.0 * (double)v[i] / (double)(sum ? sum : 1));
-			memset(v, 0, sizeof(v));
-			(void)hipMemcpyToSymbol(HIP_SYMBOL(g_f0prof), v, sizeof(v));
-		}
-	}
-#endif
-#if defined(VX_CLS_PROFILE)
-	{
-		static const char* names[5] = { "class bytes + init", "loads + sign masks", "classification", "slot allocation (+ ancestors)", "bitmap stores" };
-		unsigned long long sum = 0;
-		for (int i = 0; i < 5; ++i) sum += c->hdr[HDR_LARGE + 16 + i];
-		for (int i = 0; i < 5; ++i) fprintf(stderr, "[classify profile] %-30s %10u x16 cycles  %5.1f %%\n", names[i], c->hdr[HDR_LARGE + 16 + i], 100.0 * c->hdr[HDR_LARGE + 16 + i] / (double)(sum ? sum : 1));
-	}
-#endif
-#if defined(VX_TR_PROFILE)
-	{
-		static const char* names[11] = { "requests issued", "sign summaries + barrier", "planes to LDS + barrier", "classification + barrier", "batch bits + scan", "material wait", "list + barrier", "count + barrier", "scans + reservation", "describe + vertices", "indices" };
-		unsigned long long sum = 0;
-		for (int i = 0; i < 11; ++i) sum += c->hdr[HDR_LARGE + 16 + i];
-		for (int i = 0; i < 11; ++i) fprintf(stderr, "[transition profile] %-28s %10u x64 cycles  %5.1f %%\n", names[i], c->hdr[HDR_LARGE + 16 + i], 100.0 * c->hdr[HDR_LARGE + 16 + i] / (double)(sum ? sum : 1));
-	}
-#endif
-#if defined(VX_REG_PROFILE)
-	{
-		static const char* names[16] = { "next item", "top barrier", "begin+stage+barrier", "prefix scan", "list+barrier", "cells+barrier", "count+barrier", "vertex scan+reserve", "describe+barrier", "emit vertices", "barrier", "keep+barrier", "index scan+reserve", "stage indices+barrier", "flush indices", "record" };
-		unsigned long long sum = 0;
-		for (int i = 0; i < 16; ++i) sum += c->hdr[HDR_LARGE + 16 + i];
-		for (int i = 0; i < 16; ++i) fprintf(stderr, "[regular profile, levels >= 1] %-24s %10u kcycles  %5.1f %%\n", names[i], c->hdr[HDR_LARGE + 16 + i], 100.0 * c->hdr[HDR_LARGE + 16 + i] / (double)(sum ? sum : 1));
-	}
-#endif
-#if defined(VX_R0_PROFILE)
-	{
-		static const char* names[10] = { "top barrier", "deposit+barrier", "prefix+list+barrier", "cells", "scan barrier", "reserve+describe", "barrier", "vertices+indices", "record", "next item (drain)" };
-		unsigned long long sum = 0;
-		for (int i = 0; i < 10; ++i) sum += c->hdr[HDR_LARGE + 4 + i];
-		for (int i = 0; i < 10; ++i) fprintf(stderr, "[r0 profile] %-22s %10u kcycles  %5.1f %%\n", names[i], c->hdr[HDR_LARGE + 4 + i], 100.0 * c->hdr[HDR_LARGE + 4 + i] / (double)(sum ? sum : 1));
-	}
-#endif
 	if (hostTiming) {
 		const auto t5 = tNow();
 		fprintf(stderr, "[vx host] enqueue %.0f us, wait+events %.0f us, header %.0f us, after-header %.0f us, device %.0f us\n",

@@ -94,10 +94,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 		if (PARTIAL && l + 1u == plan.emitFrom) skipItems = matEnd[l];
 	}
 	if (PARTIAL) { regTotal = max(regTotal, skipItems) - skipItems; trTotal = max(trTotal, skipItems) - skipItems; }
-	if (VX_ABL & 4) trTotal = 0;
-	if (VX_ABL & 8) regTotal = 0;
 	const u32 upperTotal = matTotal + regTotal + trTotal;
-	const u32 total0 = (plan.level0 && !(VX_ABL & 128)) ? r0_uniform(DIRTY ? p.G.workCount[0] : p.G.slotCounts[0]) : 0u;
+	const u32 total0 = plan.level0 ? r0_uniform(DIRTY ? p.G.workCount[0] : p.G.slotCounts[0]) : 0u;
 
 	u32 tabKind = 0;          // which table image the LDS holds: 0 none, 1 regular (F0), 2 transition
 	F0Tables FT = {};
@@ -111,49 +109,24 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 	// item's first loads and is waited for with them, and a held upper item delays whoever depends on it.)
 	u32 turn = 0;
 
-#if defined(VX_MAIN_PROFILE)
-	// tools builds: where the workgroups' time goes, by role (cycles as thread 0 sees them; header words behind the large-block counter)
-	unsigned long long profTick = __builtin_readcyclecounter();
-	u32 prof[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-#define MAIN_TICK(i) do { const unsigned long long now_ = __builtin_readcyclecounter(); prof[i] += (u32)((now_ - profTick) >> 6); profTick = now_; } while (0)
-#else
-#define MAIN_TICK(i) do { } while (0)
-#endif
-#if defined(VX_MAIN_TRACE)
-	unsigned long long trT0 = 0, trT1 = 0; u32 trWhat = 0;
-#define MAIN_TRACE_END() do { if (tid0 == 0) { const u32 at_ = atomicAdd(&g_mainTraceN, 1u); if (at_ < 8192u) { unsigned long long* e_ = g_mainTrace + 18u * at_; for (u32 m_ = 0; m_ < 12u; ++m_) { e_[6u + m_] = g_marks[(blockIdx.x & 4095u) * 12u + m_]; g_marks[(blockIdx.x & 4095u) * 12u + m_] = 0; } e_[0] = trWhat; e_[1] = blockIdx.x; e_[2] = trT0; e_[3] = trT1; e_[4] = g_waitEnd[blockIdx.x & 4095u]; e_[5] = __builtin_amdgcn_s_memrealtime(); } } } while (0)
-#else
-#define MAIN_TRACE_END() do { } while (0)
-#endif
 	while (upperLeft || level0Left) {
 		MAIN_PARAMS();
-#if defined(VX_MAIN_TRACE)
-		trT0 = __builtin_amdgcn_s_memrealtime();
-#endif
 		int tid = tid0;
 		asm volatile("" : "+v"(tid)); // (per item: what a lane derives from its index alone is not hoisted out of the loop and kept in registers)
 		const bool takeUpper = upperLeft && (preferUpper || !level0Left);
 		turn ^= 1u;
 		if (tid0 == 0) sh.nextItem[turn] = takeUpper ? atomicAdd(p.G.upperHead, 1u) : atomicAdd(p.G.level0Head, plan.batch);
 		__syncthreads(); // the previous item is done (with the LDS state), and the ticket is there
-		MAIN_TICK(0);
 		if (!takeUpper) {
 			// ---- a batch of consecutive level-0 slots -----------------------------------------------------------------
 			const u32 first = r0_uniform(sh.nextItem[turn]);
 			if (first >= total0) { level0Left = false; continue; }
 			if (tabKind != 1u) { FT = f0_stage_tables(tab, p.tables, (u32)tid); tabKind = 1u; } // (visible after the walk's first barrier)
-			MAIN_TICK(1);
-#if defined(VX_MAIN_TRACE)
-			trT1 = __builtin_amdgcn_s_memrealtime(); trWhat = first; if (tid0 == 0) g_waitEnd[blockIdx.x & 4095u] = 0;
-#endif
-			f0_walk<REG_CAP_SMALL, false, !DIRTY>(p, FT, *(Fast0State<REG_CAP_SMALL>*)state, wgStats, sh.zeroFlag0, parity0, total0, 0u, first, 1u, min(first + plan.batch, total0), tid);
-			MAIN_TICK(2);
-			MAIN_TRACE_END();
+			f0_walk<REG_CAP_SMALL, false, !DIRTY>(FT, *(Fast0State<REG_CAP_SMALL>*)state, wgStats, sh.zeroFlag0, parity0, total0, 0u, first, 1u, min(first + plan.batch, total0), tid);
 			continue;
 		}
 		// ---- one item of the upper queue (a few thousand items per run) ---------------------------------------------------
 		const u32 item = r0_uniform(sh.nextItem[turn]);
-		MAIN_TICK(1);
 		if (item >= upperTotal) { upperLeft = false; continue; }
 		// item -> (kind, level, slot): the position inside its segment, looked up in the level boundaries
 		const bool isMat = item < matTotal, isReg = !isMat && item < matTotal + regTotal;
@@ -163,9 +136,6 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 		for (u32 l = 1; l + 1 < MAX_LEVELS; ++l) if (f >= matEnd[l]) { level = l + 1; base = matEnd[l]; }
 		u32 slot = f - base;
 		if (DIRTY) slot = r0_uniform(p.G.workItems[level][slot]);
-#if defined(VX_MAIN_TRACE)
-		trT1 = __builtin_amdgcn_s_memrealtime(); trWhat = ((isMat ? 1u : (isReg ? 2u : 3u)) << 28) | (level << 24) | slot; if (tid0 == 0) g_waitEnd[blockIdx.x & 4095u] = 0;
-#endif
 		if (isMat) {
 			if (DIRTY) {
 				mat_block<true>(p, level, slot, *(MatLds*)state, tid, false, plan.boxLo[level - 1u], plan.boxHi[level - 1u]);
@@ -174,9 +144,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 			} else if (PARTIAL)
 				mat_block<true, true>(p, level, slot, *(MatLds*)state, tid, true, nullptr, nullptr, plan.emitFrom);
 			else
-				mat_block<true>(p, level, slot, *(MatLds*)state, tid, (VX_ABL & 256) ? false : plan.level0 != 0u);
-			MAIN_TICK(3);
-			MAIN_TRACE_END();
+				mat_block<true>(p, level, slot, *(MatLds*)state, tid, plan.level0 != 0u);
 			continue;
 		}
 		const LevelDesc& L = p.levels[level];
@@ -186,15 +154,12 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 		if (isReg) {
 			if (tabKind != 1u) { FT = f0_stage_tables(tab, p.tables, (u32)tid); tabKind = 1u; } // (behind the barriers of the dequeue; visible after the block's first barrier)
 			f1_block<REG_CAP_SMALL, true>(p, FT, smp, *(Fast1State<REG_CAP_SMALL>*)state, wgStats, zeroFlag, parity, level, slot, coord, 0u, 0u, tid);
-			MAIN_TICK(4);
 		} else {
 			if (tabKind != 2u) { TT = stage_transition_tables(tab, p.tables, (u32)tid); tabKind = 2u; }
 			RegBlockCtx b;
 			b.level = level; b.slot = slot;
 			tr_block<false, true>(p, b, coord, *(TrState*)state, TT, scanScratch, quietFaces, quietParity, smp, tid, false);
-			MAIN_TICK(5);
 		}
-		MAIN_TRACE_END();
 	}
 	__syncthreads();
 	{
@@ -202,10 +167,6 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 		asm volatile("" : "+v"(tid)); // (the address is formed here, not carried through the kernel)
 		if (tid < 20 && wgStats[tid]) atomicAdd(&p.G.stats[tid], wgStats[tid]);
 	}
-#if defined(VX_MAIN_PROFILE)
-	MAIN_TICK(6);
-	if (tid0 == 0) for (int i = 0; i < 8; ++i) if (prof[i]) atomicAdd(&p.G.largeBlocks[4 + i], prof[i]);
-#endif
 }
 
 } // namespace

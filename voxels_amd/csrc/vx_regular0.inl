@@ -497,23 +497,11 @@ __device__ __forceinline__ bool r0_next_item(const ExecParamsDev& p, const Level
 	}
 }
 
-// Optional in-kernel phase profile (build with -DVX_R0_PROFILE, tools only): cycles between the marks, summed over the
-// blocks a workgroup handles as seen by its thread 0, land in the header words behind the large-block counter.
-#if defined(VX_R0_PROFILE)
-#define R0_TICK(i) do { const unsigned long long now_ = __builtin_readcyclecounter(); prof[i] += (u32)(now_ - tick); tick = now_; } while (0)
-#else
-#define R0_TICK(i) do { } while (0)
-#endif
-
 // The pass as workgroup `first` of `stride` (a launch of its own: k_regular0 below; the slots the table-driven pass handed
 // on are also walked by the first workgroups of k_tail).  Returns whether the workgroup wrote anything.
 template <int CAP, int MODE>
 __device__ __forceinline__ bool regular0_pass(const ExecParamsDev& p, u32 lo, const u32 first, const u32 stride)
 {
-#if defined(VX_R0_PROFILE)
-	u32 prof[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-	unsigned long long tick = __builtin_readcyclecounter();
-#endif
 	typedef Reg0State<CAP> ST;
 	typedef R0<CAP> K;
 	if (lo && *p.G.largeBlocks == 0) return false; // nothing for the 4096-cell class (uniform over the grid)
@@ -544,13 +532,10 @@ __device__ __forceinline__ bool regular0_pass(const ExecParamsDev& p, u32 lo, co
 	while (have) {
 		const u32 candIt = it + stride;
 		R0Candidate cand = { 0u, 0u, 0u, 0u, 0u };
-		R0_TICK(9);
 		__syncthreads(); // the previous block is done with the LDS state (and the tables are staged)
-		R0_TICK(0);
 		K::deposit(st, g, L, cur, pf);
 		if (tid == 0) st.degenerate = 0;
 		__syncthreads();
-		R0_TICK(1);
 
 		// ---- popcount prefix of the bitmap (every wave computes all of it: no exchange), compact cell list ----------
 		{
@@ -580,7 +565,6 @@ __device__ __forceinline__ bool regular0_pass(const ExecParamsDev& p, u32 lo, co
 			}
 		}
 		__syncthreads();
-		R0_TICK(2);
 
 		// ---- cells: lane owns `per` consecutive compact cells -----------------------------------------------------
 		const u32 nt = r0_uniform(st.wordPrefix[128]);
@@ -591,12 +575,10 @@ __device__ __forceinline__ bool regular0_pass(const ExecParamsDev& p, u32 lo, co
 			K::cell(st, RT, T, L, cur, k, wgStats);
 			sum += st.cellC[k];
 		}
-		R0_TICK(3);
 		{
 			const u32 incl = wave_inclusive_scan(sum);
 			if ((tid & 63) == 63) st.waveTot[tid >> 6] = incl;
 			__syncthreads();
-			R0_TICK(4);
 			u32 waveBase = 0, tot = 0;
 #pragma unroll
 			for (int w = 0; w < WG / 64; ++w) {
@@ -620,9 +602,7 @@ __device__ __forceinline__ bool regular0_pass(const ExecParamsDev& p, u32 lo, co
 				run += v;
 			}
 		}
-		R0_TICK(5);
 		__syncthreads();
-		R0_TICK(6);
 
 		const u32 vTotalU = r0_uniform(st.vTotal), iTotalU = r0_uniform(st.iTotal);
 		const bool room = r0_uniform(st.vOff) + vTotalU <= p.P.vertCap && r0_uniform(st.iOff) + iTotalU <= p.P.idxCap;
@@ -650,7 +630,6 @@ __device__ __forceinline__ bool regular0_pass(const ExecParamsDev& p, u32 lo, co
 			}
 		}
 		if (!requested) { if (haveNext) K::request(g, L, nxt, pf); cand = r0_peek<MODE>(p, L, total, candIt); }
-		R0_TICK(7);
 		if (tid == 0) {
 			BlockRecord& r = L.records[cur.slot];
 			r.coordId = cur.coord;
@@ -667,14 +646,10 @@ __device__ __forceinline__ bool regular0_pass(const ExecParamsDev& p, u32 lo, co
 		cur = nxt;
 		have = haveNext;
 		it = candIt;
-		R0_TICK(8);
 		haveNext = have && r0_next_item<CAP, MODE>(p, L, total, lo, stride, it, cand, nxt);
 	}
 	__syncthreads();
 	if (tid < 20 && wgStats[tid]) atomicAdd(&p.G.stats[tid], wgStats[tid]);
-#if defined(VX_R0_PROFILE)
-	if (tid == 0) for (int i = 0; i < 10; ++i) atomicAdd(&p.G.largeBlocks[4 + i], prof[i] >> 10); // units of 1024 cycles
-#endif
 	return wrote;
 }
 
