@@ -189,6 +189,46 @@ int vx_grid_inject_ball(vx_ctx* ctx, const float position[3], const float extent
 int vx_grid_inject_material(vx_ctx* ctx, const float position[3], const float extents[3], uint8_t material,
                             int add_subtract_blend, float out_min[3], float out_max[3]);
 
+/* vx_grid_inject_brushes: an ORDERED batch of brushes applied in one device pass (HIP library only).  The grid afterwards -
+ * distances, materials, blends - and the BF_Empty flags are byte for byte what `count` single-brush calls in array order
+ * leave; for the shapes without a single-brush entry point that call is Grid::InjectSurface with a VoxelSurface that
+ * evaluates f below at the sample positions p (relative to `position`, grid axes, Z up).  Float32, one rounding per
+ * operation, dot(u, v) = (u.x*v.x + u.y*v.y) + u.z*v.z (voxels_amd/csrc/tv_brush.h is the specification):
+ *   VX_BRUSH_BALL      f = sqrt(dot(p, p)) - radius                                     (= vx_grid_inject_ball)
+ *   VX_BRUSH_CAPSULE   pa = p - a, ba = b - a, h = clamp(dot(pa, ba) / dot(ba, ba), 0, 1), h = 0 when dot(ba, ba) == 0,
+ *                      v = pa - ba * h, f = sqrt(dot(v, v)) - radius                    (a, b relative to `position`)
+ *   VX_BRUSH_BOX       q = |p| - a, m = max(q, 0), f = (sqrt(dot(m, m)) + min(max(q.x, max(q.y, q.z)), 0)) - radius
+ *   VX_BRUSH_MATERIAL  Grid::InjectMaterial                                             (= vx_grid_inject_material)
+ * `extents` is the box the brush rewrites (position -+ extents / 2), as in the single-brush calls; a distance brush only
+ * changes what lies inside it, whatever the shape.  BF_Empty is recomputed for every block that at least one distance brush
+ * touches (the position -+ extents block test); blocks that only material brushes touch keep their flag.
+ * results (may be NULL) receives per brush the box the single-brush call hands back and the number of blocks it touched;
+ * union_min / union_max (may be NULL) the componentwise min / max of those boxes over the brushes that touched a block - one
+ * box to feed to vx_polygonize_dirty - or zeros when no brush touched the grid (the call then changes nothing);
+ * touched_blocks (may be NULL) the number of distinct blocks touched.
+ * Every brush is checked before anything is launched: VX_ERR_INVALID, with the grid untouched, for an unknown shape or type
+ * (MATERIAL: type is add_subtract_blend, 0 or 1), a float field that is not finite, a material above 255, a NULL array with
+ * count > 0, or a context that does not own a whole grid (vx_grid_upload / vx_grid_upload_packed).  count = 0 is VX_OK and
+ * does nothing.  Accepted count: up to VX_BRUSH_MAX_COUNT (2^24).  The call waits for the device once, at its end. */
+#define VX_BRUSH_BALL     0u
+#define VX_BRUSH_CAPSULE  1u
+#define VX_BRUSH_BOX      2u
+#define VX_BRUSH_MATERIAL 3u
+#define VX_BRUSH_MAX_COUNT (1u << 24)
+typedef struct vx_brush {          /* 64 bytes */
+    float position[3]; uint32_t shape;      /* VX_BRUSH_* */
+    float extents[3];  uint32_t type;       /* InjectionType 0..2; MATERIAL: add_subtract_blend 0 / 1 */
+    float a[3];        float radius;        /* CAPSULE: segment start; BOX: half sizes | BALL, CAPSULE: radius; BOX: rounding */
+    float b[3];        uint32_t material;   /* CAPSULE: segment end | MATERIAL: the material id */
+} vx_brush;
+typedef struct vx_brush_result {   /* 32 bytes */
+    float out_min[3], out_max[3];           /* exactly what the single-brush call hands back (output order, Y-up) */
+    uint32_t touched_blocks;                /* blocks of the position -+ extents test; 0 = the brush missed the grid */
+    uint32_t reserved;
+} vx_brush_result;
+int vx_grid_inject_brushes(vx_ctx* ctx, const vx_brush* brushes, uint32_t count, vx_brush_result* results,
+                           float union_min[3], float union_max[3], uint32_t* touched_blocks);
+
 /* MaterialMap::GetMaterial resolved on the host (include/MaterialMap.h:19-30): lut[id] = {DiffuseIds0[3],
  * DiffuseIds1[3]}, valid[id] == 0 means GetMaterial returned NULL (texture bytes stay 0). */
 int vx_material_lut(vx_ctx* ctx, const uint8_t* lut /*256*6*/, const uint8_t* valid /*256*/);

@@ -31,6 +31,12 @@ POINT_QUERY_DTYPE = np.dtype([("pos", "<f4", 3), ("max_dist", "<f4")])
 POINT_HIT_DTYPE = np.dtype([("dist", "<f4"), ("point", "<f4", 3), ("nrm", "<f4", 3), ("bary", "<f4", 2),
                             ("entry", "<u4"), ("block_id", "<u4"), ("tri", "<u4")])
 assert SPHERE_CAST_DTYPE.itemsize == 48 and SPHERE_HIT_DTYPE.itemsize == 64
+# vx_brush / vx_brush_result (include/voxels_hip.h, "edits on the device")
+BRUSH_BALL, BRUSH_CAPSULE, BRUSH_BOX, BRUSH_MATERIAL = 0, 1, 2, 3
+BRUSH_DTYPE = np.dtype([("position", "<f4", 3), ("shape", "<u4"), ("extents", "<f4", 3), ("type", "<u4"),
+                        ("a", "<f4", 3), ("radius", "<f4"), ("b", "<f4", 3), ("material", "<u4")])
+BRUSH_RESULT_DTYPE = np.dtype([("out_min", "<f4", 3), ("out_max", "<f4", 3), ("touched_blocks", "<u4"), ("reserved", "<u4")])
+assert BRUSH_DTYPE.itemsize == 64 and BRUSH_RESULT_DTYPE.itemsize == 32
 assert POINT_QUERY_DTYPE.itemsize == 16 and POINT_HIT_DTYPE.itemsize == 48
 SPHERE_STARTED_IN_CONTACT = 1
 # vx_lod_params / vx_lod_draw / vx_draw_indexed / vx_lod_counts (include/voxels_hip.h, LOD selection)
@@ -201,6 +207,11 @@ class HipLibrary:
             for name in ("vx_spherecast_device", "vx_spherecast", "vx_closest_point_device", "vx_closest_point"):
                 getattr(lib, name).argtypes = [vp, u32, vp, u32, vp]
                 getattr(lib, name).restype = C.c_int
+        # brush batches: HIP builds only, likewise
+        self.has_brushes = hasattr(lib, "vx_grid_inject_brushes")
+        if self.has_brushes:
+            lib.vx_grid_inject_brushes.argtypes = [vp, vp, u32, vp, vp, vp, vp]
+            lib.vx_grid_inject_brushes.restype = C.c_int
         self.has_lod = hasattr(lib, "vx_lod_select")
         if self.has_lod:
             lib.vx_lod_select_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
@@ -208,6 +219,22 @@ class HipLibrary:
         self.lib = lib
         self.path = path
         self.backend = lib.vx_backend().decode()
+
+
+def capsule_stroke(p0, p1, radius, inj_type=2, margin=2.0):
+    """One capsule brush for a tool of `radius` moved from p0 to p1 (grid coordinates, Z up): positioned at the middle of the
+    segment, the ends relative to it, rewriting the segment's box grown by radius + margin on every side."""
+    p0 = np.asarray(p0, np.float32); p1 = np.asarray(p1, np.float32)
+    b = np.zeros(1, BRUSH_DTYPE)
+    mid = (p0 + p1) * np.float32(0.5)
+    b["position"] = mid
+    b["shape"] = BRUSH_CAPSULE
+    b["extents"] = np.abs(p1 - p0) + np.float32(2.0 * (radius + margin))
+    b["type"] = inj_type
+    b["a"] = p0 - mid
+    b["b"] = p1 - mid
+    b["radius"] = radius
+    return b[0]
 
 
 class Level:
@@ -316,6 +343,20 @@ class Polygonizer:
         mn, mx = np.zeros(3, np.float32), np.zeros(3, np.float32)
         self._check(self._lib.vx_grid_inject_material(self._h, _ptr(pos), _ptr(ext), int(material), int(bool(add)), _ptr(mn), _ptr(mx)), "vx_grid_inject_material")
         return mn, mx
+
+    def inject_brushes(self, brushes):
+        """vx_grid_inject_brushes: a BRUSH_DTYPE array applied in array order in one device pass ->
+        (results BRUSH_RESULT_DTYPE array, union_min, union_max, distinct touched blocks)."""
+        if not self._L.has_brushes:
+            raise VoxelsHipError("this library has no brush batches (HIP builds only)")
+        brushes = np.ascontiguousarray(brushes, BRUSH_DTYPE)
+        results = np.zeros(brushes.size, BRUSH_RESULT_DTYPE)
+        mn, mx = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        touched = C.c_uint32()
+        self._check(self._lib.vx_grid_inject_brushes(self._h, _ptr(brushes) if brushes.size else None, brushes.size,
+                                                     _ptr(results) if brushes.size else None, _ptr(mn), _ptr(mx), C.byref(touched)),
+                    "vx_grid_inject_brushes")
+        return results, mn, mx, int(touched.value)
 
     def compact_pools(self):
         self._check(self._lib.vx_compact_pools(self._h), "vx_compact_pools")

@@ -3986,6 +3986,7 @@ struct Backend {
 } // namespace
 
 #include "vx_host.inl"
+#include "vx_brush.inl"
 #include "vx_ray.inl"
 #include "vx_shape.inl"
 #include "vx_lod.inl"

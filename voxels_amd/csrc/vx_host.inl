@@ -145,6 +145,9 @@ struct vx_ctx {
 	void* lodState = nullptr;
 	void (*lodFree)(vx_ctx*) = nullptr;
 	u32 firstMeshedLevel = 0;
+	// brush batches (vx_brush.inl): its device buffers
+	void* brushState = nullptr;
+	void (*brushFree)(vx_ctx*) = nullptr;
 };
 
 // every entry point makes the context's device the calling thread's current device (the HIP current device is per thread)
@@ -766,6 +769,7 @@ void vx_ctx_destroy(vx_ctx* c)
 	c->be.free(c->dScratch);
 	if (c->rayFree) c->rayFree(c);
 	if (c->lodFree) c->lodFree(c);
+	if (c->brushFree) c->brushFree(c);
 	c->be.shutdown();
 	delete c;
 }
