@@ -229,6 +229,65 @@ typedef struct vx_brush_result {   /* 32 bytes */
 int vx_grid_inject_brushes(vx_ctx* ctx, const vx_brush* brushes, uint32_t count, vx_brush_result* results,
                            float union_min[3], float union_max[3], uint32_t* touched_blocks);
 
+/* ---- detached solid pieces (HIP library only) -------------------------------------------------------------------------
+ * vx_grid_islands answers "did that carve cut something loose?" on the resident grid: the connected components of the solid
+ * voxels of a box, which of them hang in the air, and - on request - their removal.  The reference has nothing like it.
+ *   Solid      a voxel whose distance sample is < 0 (the sign bit the case codes read); zero is air.
+ *   Region     a box of voxels [lo, hi) in grid coordinates (internal axes, Z up, as vx_grid_inject_ball takes them),
+ *              lo < hi <= n per axis, not necessarily aligned to blocks; whole_grid != 0 means the whole grid.  Its volume
+ *              V = ex * ey * ez must be <= 2^30 (a whole 1024^3 grid fits; larger grids are queried box by box).
+ *   Component  a maximal set of solid voxels of the region connected through shared faces (6-connectivity) by paths INSIDE
+ *              the region.  Edge and corner contact does not connect; two arms that only join outside the region are two
+ *              components.
+ *   Label      the least region-local linear index ((z - lo.z) * ey + (y - lo.y)) * ex + (x - lo.x) over the component's
+ *              voxels.  Records are sorted by label ascending.  Nothing in the result depends on scheduling.
+ *   Faces      bit k of `faces` is set when a voxel of the component lies on region face k; order -x, +x, -y, +y, -z, +z.
+ *   Detached   (faces & anchor_faces) == 0.  0x3F: any face anchors; an application that treats only the bottom and the
+ *              sides of a box around a carve as "the world" clears the +z bit (0x1F).
+ *   Removal    (VX_ISLANDS_REMOVE) every detached component with voxels <= max_voxels (0 = no limit) has the distance of
+ *              each of its voxels set to air_value (1..127).  Materials and blends stay.  BF_Empty is recomputed by the
+ *              codec's rule for every block that held a removed voxel and for no other block, and the brick mirrors follow.
+ *              out_min / out_max (may be NULL) receive the dirty box in the convention of the edits: output order
+ *              (x, z, y), floats; for removed voxels spanning a..b inclusive per internal axis it is [a, b + 1] clamped to
+ *              [0, n] - feed it to vx_polygonize_dirty.  Zeros when nothing was removed; the call then changes nothing.
+ *              Removal does not depend on `capacity`.
+ * islands (host array; may be NULL when capacity is 0) receives the first `capacity` listed records in label order: all
+ * components, or only the detached ones with VX_ISLANDS_DETACHED_ONLY.  counts is always written; counts->listed is what an
+ * unlimited capacity would hold.  VX_ERR_OVERFLOW when listed > capacity, after everything else has been done (as
+ * vx_lod_select).  d_labels (optional; device memory, V uint32, 16-byte aligned) receives the label of every region voxel, x
+ * fastest inside the region, UINT32_MAX for air; the labels describe the grid BEFORE a removal.  The library uses the buffer as
+ * its working volume.
+ * VX_ERR_INVALID, with the grid untouched and before anything is launched, for: a null query or null counts, a bad or too
+ * large box, unknown flag bits, anchor_faces > 0x3F, air_value outside 1..127 while VX_ISLANDS_REMOVE is set, a capacity
+ * without an array, a misaligned d_labels, a context that does not own a whole grid.  VX_ERR_DEVICE, grid untouched, when
+ * working memory cannot be allocated.
+ * Working memory, kept with the context and only ever grown: 4 bytes per region voxel (none of that when d_labels is given -
+ * a whole 1024^3 query without d_labels takes 4 GiB), 4 bytes per x-row of the region (ey * ez), 4 bytes per block of the
+ * region and about 100 bytes per component.
+ * The call is synchronous and runs on the context's stream (vx_set_stream).  It waits for the device when it has counted the
+ * components (the records are sized by that number), at its end, and once more between the two when a removal changed
+ * blocks (their number sizes the flag and mirror pass). */
+#define VX_ISLANDS_DETACHED_ONLY 1u   /* list only detached components */
+#define VX_ISLANDS_REMOVE        2u
+typedef struct vx_island_query {     /* 48 bytes */
+    uint32_t lo[3], hi[3];           /* ignored when whole_grid != 0 */
+    uint32_t whole_grid, flags, anchor_faces;
+    int32_t  air_value;
+    uint64_t max_voxels;
+} vx_island_query;
+typedef struct vx_island {           /* 40 bytes */
+    uint32_t label, faces;
+    uint64_t voxels;
+    uint32_t min[3], max[3];         /* grid coordinates, inclusive */
+} vx_island;
+typedef struct vx_island_counts {    /* 48 bytes */
+    uint64_t solid_voxels, detached_voxels, removed_voxels;
+    uint32_t components, detached, listed /* what unlimited capacity would hold */, removed;
+    uint32_t touched_blocks /* blocks rewritten by removal */, reserved;
+} vx_island_counts;
+int vx_grid_islands(vx_ctx* ctx, const vx_island_query* query, vx_island* islands, uint32_t capacity,
+                    vx_island_counts* counts, uint32_t* d_labels, float out_min[3], float out_max[3]);
+
 /* MaterialMap::GetMaterial resolved on the host (include/MaterialMap.h:19-30): lut[id] = {DiffuseIds0[3],
  * DiffuseIds1[3]}, valid[id] == 0 means GetMaterial returned NULL (texture bytes stay 0). */
 int vx_material_lut(vx_ctx* ctx, const uint8_t* lut /*256*6*/, const uint8_t* valid /*256*/);

@@ -37,6 +37,14 @@ BRUSH_DTYPE = np.dtype([("position", "<f4", 3), ("shape", "<u4"), ("extents", "<
                         ("a", "<f4", 3), ("radius", "<f4"), ("b", "<f4", 3), ("material", "<u4")])
 BRUSH_RESULT_DTYPE = np.dtype([("out_min", "<f4", 3), ("out_max", "<f4", 3), ("touched_blocks", "<u4"), ("reserved", "<u4")])
 assert BRUSH_DTYPE.itemsize == 64 and BRUSH_RESULT_DTYPE.itemsize == 32
+# vx_island_query / vx_island / vx_island_counts (include/voxels_hip.h, "detached solid pieces")
+ISLANDS_DETACHED_ONLY, ISLANDS_REMOVE = 1, 2
+ISLAND_QUERY_DTYPE = np.dtype([("lo", "<u4", 3), ("hi", "<u4", 3), ("whole_grid", "<u4"), ("flags", "<u4"), ("anchor_faces", "<u4"),
+                               ("air_value", "<i4"), ("max_voxels", "<u8")])
+ISLAND_DTYPE = np.dtype([("label", "<u4"), ("faces", "<u4"), ("voxels", "<u8"), ("min", "<u4", 3), ("max", "<u4", 3)])
+ISLAND_COUNTS_DTYPE = np.dtype([("solid_voxels", "<u8"), ("detached_voxels", "<u8"), ("removed_voxels", "<u8"), ("components", "<u4"),
+                                ("detached", "<u4"), ("listed", "<u4"), ("removed", "<u4"), ("touched_blocks", "<u4"), ("reserved", "<u4")])
+assert ISLAND_QUERY_DTYPE.itemsize == 48 and ISLAND_DTYPE.itemsize == 40 and ISLAND_COUNTS_DTYPE.itemsize == 48
 assert POINT_QUERY_DTYPE.itemsize == 16 and POINT_HIT_DTYPE.itemsize == 48
 SPHERE_STARTED_IN_CONTACT = 1
 # vx_lod_params / vx_lod_draw / vx_draw_indexed / vx_lod_counts (include/voxels_hip.h, LOD selection)
@@ -212,6 +220,11 @@ class HipLibrary:
         if self.has_brushes:
             lib.vx_grid_inject_brushes.argtypes = [vp, vp, u32, vp, vp, vp, vp]
             lib.vx_grid_inject_brushes.restype = C.c_int
+        # detached solid pieces: HIP builds only, likewise
+        self.has_islands = hasattr(lib, "vx_grid_islands")
+        if self.has_islands:
+            lib.vx_grid_islands.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp]
+            lib.vx_grid_islands.restype = C.c_int
         self.has_lod = hasattr(lib, "vx_lod_select")
         if self.has_lod:
             lib.vx_lod_select_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
@@ -219,6 +232,20 @@ class HipLibrary:
         self.lib = lib
         self.path = path
         self.backend = lib.vx_backend().decode()
+
+
+def island_query(box=None, detached_only=False, remove=False, anchor_faces=0x3F, max_voxels=0, air_value=127):
+    """one ISLAND_QUERY_DTYPE record; box = (lo, hi) in grid coordinates (internal axes, Z up), None = the whole grid"""
+    q = np.zeros(1, ISLAND_QUERY_DTYPE)
+    if box is None:
+        q["whole_grid"] = 1
+    else:
+        q["lo"], q["hi"] = np.asarray(box[0], np.uint32), np.asarray(box[1], np.uint32)
+    q["flags"] = (ISLANDS_DETACHED_ONLY if detached_only else 0) | (ISLANDS_REMOVE if remove else 0)
+    q["anchor_faces"] = anchor_faces
+    q["max_voxels"] = max_voxels
+    q["air_value"] = air_value
+    return q
 
 
 def capsule_stroke(p0, p1, radius, inj_type=2, margin=2.0):
@@ -357,6 +384,43 @@ class Polygonizer:
                                                      _ptr(results) if brushes.size else None, _ptr(mn), _ptr(mx), C.byref(touched)),
                     "vx_grid_inject_brushes")
         return results, mn, mx, int(touched.value)
+
+    def islands(self, box=None, detached_only=False, remove=False, anchor_faces=0x3F, max_voxels=0, air_value=127, labels=None, capacity=None):
+        """vx_grid_islands: the connected components of the solid voxels of `box` ((lo, hi), None = the whole grid) ->
+        (records ISLAND_DTYPE array in label order, counts ISLAND_COUNTS_DTYPE record, out_min, out_max).  labels: optional torch
+        device tensor of V int32 / uint32 that receives the label volume.  capacity=None: one call with no room (and without the
+        removal) to learn `listed`, then the call proper with exactly that room."""
+        if not self._L.has_islands:
+            raise VoxelsHipError("this library has no vx_grid_islands (HIP builds only)")
+        q = island_query(box, detached_only, remove, anchor_faces, max_voxels, air_value)
+        lp = None
+        if labels is not None:
+            assert labels.is_cuda and labels.is_contiguous() and labels.element_size() == 4
+            ext = [self.n] * 3 if box is None else [int(h) - int(l) for l, h in zip(box[0], box[1])]
+            assert labels.numel() == ext[0] * ext[1] * ext[2]
+            lp = C.c_void_p(labels.data_ptr())
+        counts = np.zeros(1, ISLAND_COUNTS_DTYPE)
+        mn, mx = np.zeros(3, np.float32), np.zeros(3, np.float32)
+
+        def call(query, room):
+            recs = np.zeros(room, ISLAND_DTYPE)
+            rc = self._lib.vx_grid_islands(self._h, _ptr(query), _ptr(recs) if room else None, room, _ptr(counts), lp, _ptr(mn), _ptr(mx))
+            return rc, recs
+
+        if capacity is None:
+            # learn `listed` from a query that changes nothing, then make the call with exactly that room
+            probe = q.copy()
+            probe["flags"] &= ~np.uint32(ISLANDS_REMOVE)
+            rc, _ = call(probe, 0)
+            if rc not in (0, -3):
+                self._check(rc, "vx_grid_islands")
+            capacity = int(counts["listed"][0])
+        rc, recs = call(q, int(capacity))
+        listed = int(counts["listed"][0])
+        if rc == -3:
+            raise VoxelsHipError("vx_grid_islands failed (-3): %d records listed, room for %d" % (listed, capacity))
+        self._check(rc, "vx_grid_islands")
+        return recs[:min(listed, int(capacity))], counts[0].copy(), mn, mx
 
     def compact_pools(self):
         self._check(self._lib.vx_compact_pools(self._h), "vx_compact_pools")

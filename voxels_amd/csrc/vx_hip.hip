@@ -3987,6 +3987,7 @@ struct Backend {
 
 #include "vx_host.inl"
 #include "vx_brush.inl"
+#include "vx_island.inl"
 #include "vx_ray.inl"
 #include "vx_shape.inl"
 #include "vx_lod.inl"

@@ -148,6 +148,9 @@ struct vx_ctx {
 	// brush batches (vx_brush.inl): its device buffers
 	void* brushState = nullptr;
 	void (*brushFree)(vx_ctx*) = nullptr;
+	// detached solid pieces (vx_island.inl): its device buffers
+	void* islandState = nullptr;
+	void (*islandFree)(vx_ctx*) = nullptr;
 };
 
 // every entry point makes the context's device the calling thread's current device (the HIP current device is per thread)
@@ -770,6 +773,7 @@ void vx_ctx_destroy(vx_ctx* c)
 	if (c->rayFree) c->rayFree(c);
 	if (c->lodFree) c->lodFree(c);
 	if (c->brushFree) c->brushFree(c);
+	if (c->islandFree) c->islandFree(c);
 	c->be.shutdown();
 	delete c;
 }
