@@ -288,6 +288,58 @@ typedef struct vx_island_counts {    /* 48 bytes */
 int vx_grid_islands(vx_ctx* ctx, const vx_island_query* query, vx_island* islands, uint32_t capacity,
                     vx_island_counts* counts, uint32_t* d_labels, float out_min[3], float out_max[3]);
 
+/* ---- smoothing (HIP library only) -------------------------------------------------------------------------------------
+ * vx_grid_smooth softens what is there: an ORDERED batch of smoothing ops on the distance samples of the resident grid, each
+ * a number of Jacobi iterations of a 3x3x3 binomial filter over a box, blended in by a weight.  The reference has nothing like
+ * it.  voxels_amd/csrc/tv_smooth.h is the arithmetic; tests/smooth_oracle.py states this text again in numpy.
+ *   One iteration of one op.  Every read sees the grid as it was before this iteration.  For each voxel v of the box [lo, hi):
+ *     S      = sum over dx, dy, dz in {-1, 0, 1} of k(dx) k(dy) k(dz) d(clamp(v + (dx, dy, dz), 0, n - 1)), k = (1, 2, 1): an
+ *              exact integer.  d is the int8 distance sample as stored (-128 is legal input).  Neighbours outside the BOX are
+ *              read from the grid - fixed boundary values; neighbours outside the GRID clamp to the edge voxel.
+ *     w      = strength when radius == 0; otherwise, in float32 with one rounding per written operation:
+ *              p = (float)v - center, r = sqrtf((p.x p.x + p.y p.y) + p.z p.z), q = 1.0f - r / radius,
+ *              w = strength * (q > 0 ? q : 0)
+ *     new    = (int8) clamp(rintf(f), -128, 127), t = (float)S * 0.015625f, f = (float)d + w * (t - (float)d); rintf rounds
+ *              to nearest, ties to even; the clamp is never active for strength in 0..1; a result of -0 is 0, which is air.
+ *     Materials and blends are untouched.
+ *   Iterations `iterations` repeats the step on the same box: iteration i + 1 reads the result of iteration i inside the box
+ *              and the unchanged grid outside it.
+ *   Batches    the ops are applied in array order; the grid afterwards is byte for byte what `count` single-op calls leave.
+ *              An op with iterations == 0 or strength == 0 changes nothing and reports a zero box.
+ *   Flags      BF_Empty is recomputed by the codec's rule for every block that the box of an op with iterations >= 1 and
+ *              strength > 0 intersects, and for no other block; the brick mirrors follow: a polygonization after the call
+ *              needs no vx_grid_invalidate.
+ *   Results    results[i] (may be NULL) receives the box of the voxels whose value op i actually changed - the end of the op
+ *              compared with its beginning - in the convention of vx_grid_islands: output order (x, z, y), floats; for changed
+ *              voxels spanning a..b inclusive per internal axis it is [a, b + 1] clamped to [0, n]; zeros when nothing changed;
+ *              and the number of those voxels.  union_min / union_max (may be NULL): the componentwise union over the ops that
+ *              changed something - the one box to feed to vx_polygonize_dirty - or zeros.  changed_voxels (may be NULL): the
+ *              sum of the per-op counts.
+ * Everything is checked before anything is launched: VX_ERR_INVALID, with the grid untouched, for a NULL array with count > 0,
+ * lo >= hi or hi > n on any axis, a center, radius or strength that is not finite, radius < 0, strength outside [0, 1],
+ * iterations > VX_SMOOTH_MAX_ITERATIONS, count > VX_SMOOTH_MAX_COUNT, or a context that does not own a whole grid
+ * (vx_grid_upload / vx_grid_upload_packed).  count = 0 is VX_OK and does nothing.  VX_ERR_DEVICE, grid untouched, when working
+ * memory cannot be allocated.
+ * The call runs on the context's stream (vx_set_stream) and waits for the device once, at its end, to read the results.
+ * Working memory, kept with the context and only ever grown: one byte per voxel of the largest box rounded up to whole 16^3
+ * grid blocks (twice that when an op has more than one iteration: its original values are kept for the comparison), 4 bytes
+ * per block of that box and 64 bytes per op. */
+#define VX_SMOOTH_MAX_ITERATIONS 64u
+#define VX_SMOOTH_MAX_COUNT (1u << 16)
+typedef struct vx_smooth {          /* 48 bytes */
+    uint32_t lo[3], hi[3];          /* box [lo, hi) in grid coordinates, internal axes (Z up), as vx_island_query */
+    float    center[3];             /* falloff centre, grid coordinates, may be fractional / outside the box */
+    float    radius;                /* > 0: ball falloff; == 0: uniform weight over the box */
+    float    strength;              /* 0..1 */
+    uint32_t iterations;            /* 0..VX_SMOOTH_MAX_ITERATIONS */
+} vx_smooth;
+typedef struct vx_smooth_result {   /* 32 bytes */
+    float    out_min[3], out_max[3];
+    uint64_t changed_voxels;
+} vx_smooth_result;
+int vx_grid_smooth(vx_ctx* ctx, const vx_smooth* ops, uint32_t count, vx_smooth_result* results /* may be NULL */,
+                   float union_min[3], float union_max[3] /* may be NULL */, uint64_t* changed_voxels /* may be NULL */);
+
 /* MaterialMap::GetMaterial resolved on the host (include/MaterialMap.h:19-30): lut[id] = {DiffuseIds0[3],
  * DiffuseIds1[3]}, valid[id] == 0 means GetMaterial returned NULL (texture bytes stay 0). */
 int vx_material_lut(vx_ctx* ctx, const uint8_t* lut /*256*6*/, const uint8_t* valid /*256*/);

@@ -45,6 +45,11 @@ ISLAND_DTYPE = np.dtype([("label", "<u4"), ("faces", "<u4"), ("voxels", "<u8"), 
 ISLAND_COUNTS_DTYPE = np.dtype([("solid_voxels", "<u8"), ("detached_voxels", "<u8"), ("removed_voxels", "<u8"), ("components", "<u4"),
                                 ("detached", "<u4"), ("listed", "<u4"), ("removed", "<u4"), ("touched_blocks", "<u4"), ("reserved", "<u4")])
 assert ISLAND_QUERY_DTYPE.itemsize == 48 and ISLAND_DTYPE.itemsize == 40 and ISLAND_COUNTS_DTYPE.itemsize == 48
+# vx_smooth / vx_smooth_result (include/voxels_hip.h, "smoothing")
+SMOOTH_MAX_ITERATIONS, SMOOTH_MAX_COUNT = 64, 1 << 16
+SMOOTH_DTYPE = np.dtype([("lo", "<u4", 3), ("hi", "<u4", 3), ("center", "<f4", 3), ("radius", "<f4"), ("strength", "<f4"), ("iterations", "<u4")])
+SMOOTH_RESULT_DTYPE = np.dtype([("out_min", "<f4", 3), ("out_max", "<f4", 3), ("changed_voxels", "<u8")])
+assert SMOOTH_DTYPE.itemsize == 48 and SMOOTH_RESULT_DTYPE.itemsize == 32
 assert POINT_QUERY_DTYPE.itemsize == 16 and POINT_HIT_DTYPE.itemsize == 48
 SPHERE_STARTED_IN_CONTACT = 1
 # vx_lod_params / vx_lod_draw / vx_draw_indexed / vx_lod_counts (include/voxels_hip.h, LOD selection)
@@ -225,6 +230,11 @@ class HipLibrary:
         if self.has_islands:
             lib.vx_grid_islands.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp]
             lib.vx_grid_islands.restype = C.c_int
+        # smoothing: HIP builds only, likewise
+        self.has_smooth = hasattr(lib, "vx_grid_smooth")
+        if self.has_smooth:
+            lib.vx_grid_smooth.argtypes = [vp, vp, u32, vp, vp, vp, vp]
+            lib.vx_grid_smooth.restype = C.c_int
         self.has_lod = hasattr(lib, "vx_lod_select")
         if self.has_lod:
             lib.vx_lod_select_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
@@ -246,6 +256,17 @@ def island_query(box=None, detached_only=False, remove=False, anchor_faces=0x3F,
     q["max_voxels"] = max_voxels
     q["air_value"] = air_value
     return q
+
+
+def smooth_op(box, center=None, radius=0.0, strength=1.0, iterations=1):
+    """one SMOOTH_DTYPE record; box = (lo, hi) in grid coordinates (internal axes, Z up); center defaults to the middle of the
+    box (it only matters with radius > 0: the ball falloff)"""
+    op = np.zeros(1, SMOOTH_DTYPE)
+    lo, hi = np.asarray(box[0], np.uint32), np.asarray(box[1], np.uint32)
+    op["lo"], op["hi"] = lo, hi
+    op["center"] = (lo.astype(np.float32) + hi.astype(np.float32)) * np.float32(0.5) if center is None else np.asarray(center, np.float32)
+    op["radius"], op["strength"], op["iterations"] = radius, strength, iterations
+    return op
 
 
 def capsule_stroke(p0, p1, radius, inj_type=2, margin=2.0):
@@ -384,6 +405,19 @@ class Polygonizer:
                                                      _ptr(results) if brushes.size else None, _ptr(mn), _ptr(mx), C.byref(touched)),
                     "vx_grid_inject_brushes")
         return results, mn, mx, int(touched.value)
+
+    def smooth(self, ops):
+        """vx_grid_smooth: a SMOOTH_DTYPE array applied in array order ->
+        (results SMOOTH_RESULT_DTYPE array, union_min, union_max, changed voxels)."""
+        if not self._L.has_smooth:
+            raise VoxelsHipError("this library has no vx_grid_smooth (HIP builds only)")
+        ops = np.ascontiguousarray(ops, SMOOTH_DTYPE).reshape(-1)
+        results = np.zeros(ops.size, SMOOTH_RESULT_DTYPE)
+        mn, mx = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        changed = C.c_uint64()
+        self._check(self._lib.vx_grid_smooth(self._h, _ptr(ops) if ops.size else None, ops.size, _ptr(results) if ops.size else None,
+                                             _ptr(mn), _ptr(mx), C.byref(changed)), "vx_grid_smooth")
+        return results, mn, mx, int(changed.value)
 
     def islands(self, box=None, detached_only=False, remove=False, anchor_faces=0x3F, max_voxels=0, air_value=127, labels=None, capacity=None):
         """vx_grid_islands: the connected components of the solid voxels of `box` ((lo, hi), None = the whole grid) ->

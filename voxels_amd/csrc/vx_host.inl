@@ -151,6 +151,9 @@ struct vx_ctx {
 	// detached solid pieces (vx_island.inl): its device buffers
 	void* islandState = nullptr;
 	void (*islandFree)(vx_ctx*) = nullptr;
+	// smoothing (vx_smooth.inl): its device buffers
+	void* smoothState = nullptr;
+	void (*smoothFree)(vx_ctx*) = nullptr;
 };
 
 // every entry point makes the context's device the calling thread's current device (the HIP current device is per thread)
@@ -774,6 +777,7 @@ void vx_ctx_destroy(vx_ctx* c)
 	if (c->lodFree) c->lodFree(c);
 	if (c->brushFree) c->brushFree(c);
 	if (c->islandFree) c->islandFree(c);
+	if (c->smoothFree) c->smoothFree(c);
 	c->be.shutdown();
 	delete c;
 }
