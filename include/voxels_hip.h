@@ -619,6 +619,12 @@ int vx_lod_select(vx_ctx* ctx, const vx_lod_params* params, uint32_t draw_capaci
  * PerCaseCellsCount (include/Polygonizer.h:110-132) */
 int vx_stats(vx_ctx* ctx, uint32_t stats[20]);
 
+/* Transition blocks of the last run (full or incremental) by the body that meshed them: out[0] = through the table-driven
+ * body (no exact zero on the block's staged boundary planes, all its non-trivial transition cells in one batch), out[1] = through
+ * the general phases although the table-driven body is on (VX_FAST bit 2).  Both 0 with the body off.  Diagnostics: the
+ * meshes are the same either way. */
+int vx_transition_path_counts(vx_ctx* ctx, uint32_t out[2]);
+
 /* The device forms of the exactness-critical arithmetic checked exhaustively on the GPU they run on (the reference does
  * this arithmetic on the host: t = (v1 << 8) / (v1 - v0), src/TransVoxelImpl.cpp:1591; normalizeFixZero, :93-103):
  * results[0] = crossed int8 sample pairs whose t differs from the truncated quotient, results[1] = gradients whose normal

@@ -203,6 +203,7 @@ class HipLibrary:
         lib.vx_host_meshes_trim.restype = None
         lib.vx_host_meshes_reserve.argtypes = [vp, C.c_uint64, C.c_uint64]
         lib.vx_stats.argtypes = [vp, vp]
+        lib.vx_transition_path_counts.argtypes = [vp, vp]
         lib.vx_selftest.argtypes = [vp, vp]
         lib.vx_stage_layout.argtypes = [vp, C.POINTER(C.c_int)]
         lib.vx_set_stage_timing.argtypes = [vp, C.c_int]
@@ -786,3 +787,9 @@ class Polygonizer:
         out = np.zeros(20, np.uint32)
         self._check(self._lib.vx_stats(self._h, _ptr(out)), "vx_stats")
         return out
+
+    def transition_path_counts(self):
+        """vx_transition_path_counts: (table_driven, fallback) transition blocks of the last run."""
+        out = np.zeros(2, np.uint32)
+        self._check(self._lib.vx_transition_path_counts(self._h, _ptr(out)), "vx_transition_path_counts")
+        return int(out[0]), int(out[1])

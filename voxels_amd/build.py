@@ -20,7 +20,7 @@ def _newer(target, sources):
 def build_hip(force=False, verbose=True):
     """hipcc --offload-arch=gfx950 ... -o voxels_amd/csrc/libvoxels_hip.so (cross-compiles without a GPU)."""
     out = os.path.join(CSRC, "libvoxels_hip.so")
-    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_lod.inl", "tv_lod.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_tables.inc")]
+    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_lod.inl", "tv_lod.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
     srcs.append(os.path.join(ROOT, "include", "voxels_hip.h"))
     if not force and not _newer(out, srcs):
         return out
@@ -113,7 +113,7 @@ def kernel_resources(remarks):
 def build_hip_casedump(force=False):
     """Test build of the HIP library that also records the case codes it looks up (tests/test_case_codes.py)."""
     out = os.path.join(CSRC, "libvoxels_hip_casedump.so")
-    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_lod.inl", "tv_lod.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_tables.inc")]
+    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_lod.inl", "tv_lod.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
     if not force and not _newer(out, srcs):
         return out
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -125,7 +125,7 @@ def build_hip_conservative(force=False):
     """Test build of the HIP library whose in-kernel dependency flags use release / acquire fences instead of write-through
     stores and loads (-DVX_CONSERVATIVE_SYNC, vx_hip.hip): tests/test_gpu_parity.py compares it with the product library."""
     out = os.path.join(CSRC, "libvoxels_hip_conservative.so")
-    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_lod.inl", "tv_lod.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_tables.inc")]
+    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_lod.inl", "tv_lod.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
     if not force and not _newer(out, srcs):
         return out
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -194,7 +194,7 @@ def build_emu(force=False):
     d = os.path.join(ROOT, "tests", "emu")
     out = os.path.join(d, "libvoxels_emu.so")
     srcs = [os.path.join(d, "emu.cpp"), os.path.join(d, "emu_backend.inl")] + \
-           [os.path.join(CSRC, f) for f in ("vx_host.inl", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_tables.inc")]
+           [os.path.join(CSRC, f) for f in ("vx_host.inl", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
     if not force and not _newer(out, srcs):
         return out
     subprocess.check_call(["g++", "-std=c++14", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas",
@@ -254,6 +254,21 @@ def build_smooth_host(force=False):
         return out
     subprocess.check_call(["g++", "-std=c++14", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-o", out,
                            os.path.join(d, "smooth_host.cpp")], cwd=d)
+    return out
+
+
+def build_trfast_host(force=False):
+    """Host side of the tests of the table-driven transition body (csrc/tv_fastt.h): the CPU emulation of tests/emu with a
+    transition pass that runs either body, and the exhaustive check of the derived case rows - tests only
+    (tests/test_trfast_tables.py)."""
+    d = os.path.join(ROOT, "tests", "trfast")
+    out = os.path.join(d, "libvoxels_trfast_host.so")
+    srcs = [os.path.join(d, "trfast_host.cpp"), os.path.join(ROOT, "tests", "emu", "emu_backend.inl")] + \
+           [os.path.join(CSRC, f) for f in ("vx_host.inl", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
+    if not force and not _newer(out, srcs):
+        return out
+    subprocess.check_call(["g++", "-std=c++14", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas",
+                           "-Wno-subobject-linkage", "-o", out, os.path.join(d, "trfast_host.cpp")], cwd=d)
     return out
 
 

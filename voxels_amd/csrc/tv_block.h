@@ -136,7 +136,9 @@ TV_HD size_t xplane_offset(const XPlanes& P, u32 plane, u32 Z, u32 Y) { return (
 struct __attribute__((aligned(16))) FlatItem { u32 where, coordId, ntCells, pad; }; // Globals::flatItems
 
 // stats[0] = non-trivial cells, [1] = degenerate triangles removed, [2] = level-0 blocks processed,
-// stats[4..19] = per-class cell counts
+// stats[4..19] = per-class cell counts; the device header has room behind them: [STAT_TR_PATHS], [+ 1] = transition blocks of
+// the run through the table-driven body / that fell back to the general phases (GPU passes, vx_transition_path_counts)
+enum { STAT_TR_PATHS = 20 };
 struct Globals {
 	GridView grid;
 	const u8* emptyFlags;   // [cnt0^3] BF_Empty of every level-0 block (host-computed property of the Grid)
@@ -1043,6 +1045,7 @@ struct TrState {
 	                          // (one round trip less in front of the list phase) when the block's material cache is known to be complete
 	u32 faceOn;               // bit f = face has a neighbour block
 	u32 vOff, iOff, vTotal, iTotal;
+	u32 zero;                 // table-driven body (tv_fastt.h): a face that is on holds an exact zero (the word fills the struct's tail padding)
 };
 
 // end of the batch of faces starting at f0: as many consecutive faces as fit TR_CAP cells (at least one)
@@ -1270,7 +1273,38 @@ TV_HD void tr_phase_describe(TrState& st, u32 chunkBase, int tid, int nth)
 	}
 }
 
-// one lane = one new transition vertex of the chunk; `smp` reads the voxels around it (tr_new_vertex)
+// One new transition vertex: table vertex vi of compact cell k (case code and zero mask are the classification's); `smp` reads the
+// voxels around it (tr_new_vertex)
+template <typename SMP>
+TV_HD void tr_emit_vertex(const TrState& st, const Tables& T, const Globals& G, const SMP& smp, const RegBlockCtx& b, u32 k, u32 vi, u32 code, u32 zeroMask, PolyVertex* out)
+{
+	const u32 c = st.cellOf[k];
+	const int f = (int)(c >> 8), row = (int)((c >> 4) & 15), col = (int)(c & 15);
+	const FaceGeom fg = face_geom(f);
+	// of the cell's samples the vertex needs its two end points: expanded sample i sits at plane offset (dv, du) = (i / 3, i % 3)
+	// for i < 9, the low-resolution corners 9..12 are the plane's corners 0, 2, 6, 8
+	const u32 w = T.trVert(code, vi);
+	TrResolution r;
+	int corner; u32 dir, slot; bool endpoint;
+	tr_vertex_dir_slot_z(T, zeroMask, w, r.t, dir, slot, endpoint, corner);
+	r.endpoint = endpoint ? 1 : 0; r.dir = (u8)dir; r.slot = (u8)slot; r.kind = RK_NEW_EDGE; r.store = NO_SLOT;
+	const i8* cellSamples = st.plane[f] + (row * 2) * TR_PROW + col * 2;
+	const u32 e0 = (w >> 4) & 15u, e1 = w & 15u;
+	// small tables in constants: plane sample g (0..8) of expanded sample i (nibbles); row g / 3 and column g % 3 (2 bits each)
+	const u32 g0 = (u32)(0x8620876543210ull >> (4u * e0)) & 15u, g1 = (u32)(0x8620876543210ull >> (4u * e1)) & 15u;
+	const int p0 = cellSamples[((0x2A540u >> (2u * g0)) & 3u) * TR_PROW + ((0x24924u >> (2u * g0)) & 3u)];
+	const int p1 = cellSamples[((0x2A540u >> (2u * g1)) & 3u) * TR_PROW + ((0x24924u >> (2u * g1)) & 3u)];
+	TrCellGeom geo;
+	tr_cell_geom(fg, b, row, col, geo);
+	// the vertex's material id is the low-res cell's whatever the end points hold (tr_new_vertex), so its row of the
+	// material table is requested before the voxel fetches instead of behind them (one round trip less)
+	const unsigned long long lut = lut_row(G.lut, st.cellMat[k]);
+	RawVertex rv;
+	tr_new_vertex(smp, fg, geo, p0, p1, w, r, st.cellMat[k], rv);
+	pack_vertex_row(rv, lut, out);
+}
+
+// one lane = one new transition vertex of the chunk
 template <typename SMP>
 TV_HD void tr_phase_emit_vertices(TrState& st, const Tables& T, const Globals& G, const SMP& smp, const Pools& P, const RegBlockCtx& b, u32 chunkBase, int tid, int nth)
 {
@@ -1278,33 +1312,8 @@ TV_HD void tr_phase_emit_vertices(TrState& st, const Tables& T, const Globals& G
 	const u32 end = (st.vTotal - chunkBase < (u32)VDESC_CAP) ? st.vTotal - chunkBase : (u32)VDESC_CAP;
 	for (u32 j = (u32)tid; j < end; j += (u32)nth) {
 		const u32 desc = st.vdesc[j];
-		const u32 k = desc & 0x7FFu, vi = desc >> 11;
-		const u32 c = st.cellOf[k];
-		const int f = (int)(c >> 8), row = (int)((c >> 4) & 15), col = (int)(c & 15);
-		const FaceGeom fg = face_geom(f);
-		// case code and zero mask are the classification's (cellBits); of the cell's samples the vertex needs its two end points:
-		// expanded sample i sits at plane offset (dv, du) = (i / 3, i % 3) for i < 9, the low-resolution corners 9..12 are the
-		// plane's corners 0, 2, 6, 8
-		const u32 bits = st.cellBits[k];
-		const u32 w = T.trVert(bits & 0x1FFu, vi);
-		TrResolution r;
-		int corner; u32 dir, slot; bool endpoint;
-		tr_vertex_dir_slot_z(T, bits >> 9, w, r.t, dir, slot, endpoint, corner);
-		r.endpoint = endpoint ? 1 : 0; r.dir = (u8)dir; r.slot = (u8)slot; r.kind = RK_NEW_EDGE; r.store = NO_SLOT;
-		const i8* cellSamples = st.plane[f] + (row * 2) * TR_PROW + col * 2;
-		const u32 e0 = (w >> 4) & 15u, e1 = w & 15u;
-		// small tables in constants: plane sample g (0..8) of expanded sample i (nibbles); row g / 3 and column g % 3 (2 bits each)
-		const u32 g0 = (u32)(0x8620876543210ull >> (4u * e0)) & 15u, g1 = (u32)(0x8620876543210ull >> (4u * e1)) & 15u;
-		const int p0 = cellSamples[((0x2A540u >> (2u * g0)) & 3u) * TR_PROW + ((0x24924u >> (2u * g0)) & 3u)];
-		const int p1 = cellSamples[((0x2A540u >> (2u * g1)) & 3u) * TR_PROW + ((0x24924u >> (2u * g1)) & 3u)];
-		TrCellGeom geo;
-		tr_cell_geom(fg, b, row, col, geo);
-		// the vertex's material id is the low-res cell's whatever the end points hold (tr_new_vertex), so its row of the
-		// material table is requested before the voxel fetches instead of behind them (one round trip less)
-		const unsigned long long lut = lut_row(G.lut, st.cellMat[k]);
-		RawVertex rv;
-		tr_new_vertex(smp, fg, geo, p0, p1, w, r, st.cellMat[k], rv);
-		pack_vertex_row(rv, lut, P.verts + st.vOff + chunkBase + j);
+		const u32 k = desc & 0x7FFu, bits = st.cellBits[k];
+		tr_emit_vertex(st, T, G, smp, b, k, desc >> 11, bits & 0x1FFu, bits >> 9, P.verts + st.vOff + chunkBase + j);
 	}
 }
 

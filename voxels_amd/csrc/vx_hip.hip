@@ -48,6 +48,7 @@
 #include "tv_block.h"
 #include "tv_fast0.h"
 #include "tv_fast1.h"
+#include "tv_fastt.h"
 #include "vx_terrain_math.h"
 
 #define VX_BACKEND_NAME "hip:gfx950"
@@ -2181,9 +2182,11 @@ __device__ __forceinline__ void tr_planes_request(const TrLatticeT<OFF>& lat, co
 	}
 }
 
-__device__ __forceinline__ void tr_planes_store(const uint4& r0, const uint4& r1, i8 rFar, const i8 (&g)[9], bool xRows, u32 on, int tid, TrState& st)
+// (returns non-zero when a sample this lane stored is an exact zero: the table-driven body of vx_fastt.inl is for blocks without one)
+__device__ __forceinline__ u32 tr_planes_store(const uint4& r0, const uint4& r1, i8 rFar, const i8 (&g)[9], bool xRows, u32 on, int tid, TrState& st)
 {
 	asm volatile("" : "+v"(tid));
+	u32 zero = 0;
 	if (tid < (xRows ? 198 : 132)) {
 		const int fi = tid / 33, rowV = tid - fi * 33, rowFace = fi < 4 ? fi + (fi >= 2 ? 1 : 0) : (fi == 4 ? 2 : 5);
 		if ((on >> rowFace) & 1u) {
@@ -2191,27 +2194,39 @@ __device__ __forceinline__ void tr_planes_store(const uint4& r0, const uint4& r1
 			*(uint4*)dst = r0;
 			*(uint4*)(dst + 16) = r1;
 			dst[32] = rFar;
+			zero = f0_has_zero_byte(r0.x) | f0_has_zero_byte(r0.y) | f0_has_zero_byte(r0.z) | f0_has_zero_byte(r0.w)
+			     | f0_has_zero_byte(r1.x) | f0_has_zero_byte(r1.y) | f0_has_zero_byte(r1.z) | f0_has_zero_byte(r1.w) | (rFar == 0 ? 1u : 0u);
 		}
 	}
-	if (xRows) return; // (uniform)
+	if (xRows) return zero; // (uniform)
 #pragma unroll
 	for (int q = 0; q < 9; ++q) {
 		const int t = tid + q * WG;
 		if (t < 2 * PLANE) {
 			const int fi = t >= PLANE ? 1 : 0, r = t - fi * PLANE;
 			const int vv = r / 33, uu = r - vv * 33;
-			if ((on >> (fi ? 5 : 2)) & 1u) st.plane[fi ? 5 : 2][vv * TR_PROW + uu] = g[q];
+			if ((on >> (fi ? 5 : 2)) & 1u) { st.plane[fi ? 5 : 2][vv * TR_PROW + uu] = g[q]; zero |= g[q] == 0 ? 1u : 0u; }
 		}
 	}
+	return zero;
 }
+
+} // namespace
+
+#include "vx_fastt.inl"
+
+namespace {
 
 // WIDE: a brick mirror of 4 GiB or more (grids beyond 1024^3): 64-bit voxel offsets around the vertices
 // (three waves per SIMD there: the 64-bit address terms do not fit the 128 registers of four)
 // One block of a level with transition cells.  GATED (k_main): the block's material cache comes from another workgroup of the
 // same launch and is waited for where it is first read (planes, sign summaries, cell classification and scans need none of it).
+// The staging is common to two bodies: with `tables` (VX_FAST bit 2) a block without a zero on its staged planes whose cells fit
+// one batch takes the table-driven body (trf_block, vx_fastt.inl); every other block the general phases below, in place.
+// pathCount (LDS, flushed once per workgroup): [0] blocks through the table-driven body, [1] blocks that fell back.
 template <bool WIDE, bool GATED>
 __device__ __forceinline__ void tr_block(const ExecParamsDev& p, RegBlockCtx b, u32 coordId, TrState& st, const Tables& T, u32* scanScratch, u32* quietFaces, u32& quietParity,
-                                         const BrickSamplerT<typename std::conditional<WIDE, size_t, u32>::type>& smp, int tid, const bool matKnown = true)
+                                         const BrickSamplerT<typename std::conditional<WIDE, size_t, u32>::type>& smp, int tid, const bool tables, u32* pathCount, const bool matKnown = true)
 {
 	// matKnown: the block's material cache is known to be complete (the stand-alone pass: earlier launches wrote it): its entries
 	// behind the transition cells are then requested with the planes.  (Inside k_main that would need a launch-wide "all
@@ -2222,6 +2237,7 @@ __device__ __forceinline__ void tr_block(const ExecParamsDev& p, RegBlockCtx b, 
 	const LevelDesc& L = p.levels[b.level];
 	b.mult = L.mult;
 	block_coords(__builtin_amdgcn_readfirstlane(coordId), L.cnt, b.bx, b.by, b.bz);
+	if (tid == 0) st.zero = 0; // (the previous item is done with the state; set behind the next barrier, read behind the one after)
 
 	{
 		u32 on = 0;
@@ -2296,8 +2312,10 @@ __device__ __forceinline__ void tr_block(const ExecParamsDev& p, RegBlockCtx b, 
 			for (int f = 0; f < 6; ++f) st.faceMat[f * 256 + tid] = fm[f];
 		}
 		if (haveLattice) {
-			tr_planes_store(rowLo, rowHi, rowFar, xFace, lat.xp != nullptr, on, tid, st);
+			const u32 zero = tr_planes_store(rowLo, rowHi, rowFar, xFace, lat.xp != nullptr, on, tid, st);
+			if (tables && __ballot(zero != 0) && (tid & 63) == 0) st.zero = 1;
 		} else {
+			if (tid == 0) st.zero = 1; // (planes gathered sample by sample are not looked through: the general phases take the block)
 			// no resident lattice for these planes: sample by sample from the grid's mirror; 33 x 33 samples per face, three
 			// faces (15 loads per lane) in flight together (a face that is off - uniform over the workgroup - is neither
 			// requested nor stored: nothing reads its plane)
@@ -2319,7 +2337,9 @@ __device__ __forceinline__ void tr_block(const ExecParamsDev& p, RegBlockCtx b, 
 	__syncthreads();
 	tr_phase_classify(st, tid, WG);
 	__syncthreads();
-	for (int f0 = 0; f0 < 6;) {
+	const bool tableDriven = tables && trf_block<WIDE, GATED>(p, b, st, T, scanScratch, smp, tid, matReady, preMat); // (uniform)
+	if (tables && tid == 0) ++pathCount[tableDriven ? 0 : 1];
+	for (int f0 = 0; !tableDriven && f0 < 6;) {
 		const int f1 = tr_batch_end(st, f0); // uniform
 		__syncthreads();
 		tr_phase_batch_bits(st, f0, f1, tid, WG);
@@ -2379,14 +2399,16 @@ __device__ __forceinline__ void tr_block(const ExecParamsDev& p, RegBlockCtx b, 
 }
 
 template <bool WIDE>
-__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WIDE ? 3 : TR_WAVES))) void k_transition(ExecParamsDev p, u32 levels)
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WIDE ? 3 : TR_WAVES))) void k_transition(ExecParamsDev p, u32 levels, u32 tables)
 {
 	u8* tab = smem;
 	TrState& st = *(TrState*)(smem + TR_TAB_LDS);
 	__shared__ WorkList wl;
 	__shared__ u32 scanScratch[8];
 	__shared__ u32 quietFaces[2];
+	__shared__ u32 pathCount[2];
 	u32 quietParity = 0;
+	if (threadIdx.x < 2) pathCount[threadIdx.x] = 0;
 
 	// (requested first: the copy is in flight while thread 0 fetches the level counts)
 	const Tables T = stage_transition_tables(tab, p.tables, threadIdx.x); // visible after the first barrier of the item loop
@@ -2437,8 +2459,9 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WIDE ? 3 : T
 			coordId = fi.coordId;
 		}
 		b.level = __builtin_amdgcn_readfirstlane(b.level); b.slot = __builtin_amdgcn_readfirstlane(b.slot);
-		tr_block<WIDE, false>(p, b, coordId, st, T, scanScratch, quietFaces, quietParity, smp, tid);
+		tr_block<WIDE, false>(p, b, coordId, st, T, scanScratch, quietFaces, quietParity, smp, tid, tables != 0u, pathCount);
 	}
+	if (threadIdx.x < 2 && pathCount[threadIdx.x]) atomicAdd(&p.G.stats[STAT_TR_PATHS + threadIdx.x], pathCount[threadIdx.x]); // (behind the last block's closing barrier)
 }
 
 
@@ -3089,7 +3112,8 @@ struct Backend {
 	// that production runs reach through their data - dense surfaces, grids beyond 1024^3, blocks with zero samples - so that the
 	// tests can drive those paths on small fixtures (tests/test_gpu_parity.py::test_hip_runtime_knobs_select_equivalent_paths).
 	struct Tuning {
-		u32 fast = 3;        // VX_FAST: bit 0 = table-driven pass on level 0, bit 1 = on the levels >= 1 (0: every block through the general passes)
+		u32 fast = 7;        // VX_FAST: bit 0 = table-driven pass on level 0, bit 1 = on the levels >= 1 (0: every block through the general passes),
+		                     // bit 2 = table-driven body for the transition cells (vx_fastt.inl)
 		u32 forceWide = 0;   // VX_FORCE_WIDE=1: the 64-bit-offset kernel variants (grids beyond 1024^3) on small grids too
 		u32 upper = 1;       // VX_UPPER=0: the chain of launches (what dense surfaces run) instead of k_main
 		u32 selfHead = 1;    // VX_SELF_HEAD=0: a classification pass (k_classify, k_hierarchy) instead of k_run_head handing out the slots
@@ -3098,6 +3122,7 @@ struct Backend {
 		static constexpr u32 classifyRowGroup = 4, regWgsPerCu = 20, f1WgsPerCu = 20, foldBlocks = 65536, upWgsPerCu = 5, mainWgsPerCu = 4, mainBatch = 2, mainUpperNum = 1, mainUpperDen = 4;
 		bool fast0() const { return (fast & 1u) != 0; }
 		bool fast1() const { return (fast & 2u) != 0; }
+		bool fastT() const { return (fast & 4u) != 0; }
 	} tune;
 	static u32 env_u32(const char* name, u32 fallback) { const char* v = getenv(name); return v ? (u32)atoi(v) : fallback; }
 
@@ -3120,7 +3145,7 @@ struct Backend {
 		if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { err = "no HIP device"; return false; }
 		if (!check(hipSetDevice(device), "hipSetDevice")) { err = lastError; return false; }
 		this->device = device;
-		tune.fast = env_u32("VX_FAST", 3);
+		tune.fast = env_u32("VX_FAST", 7);
 		tune.forceWide = env_u32("VX_FORCE_WIDE", 0);
 		tune.upper = env_u32("VX_UPPER", 1);
 		tune.selfHead = env_u32("VX_SELF_HEAD", 1);
@@ -3672,6 +3697,7 @@ struct Backend {
 		plan.fastEnd = std::min<u32>(levels, PYRAMID_LEVELS);
 		plan.level0 = withLevel0 ? 1u : 0u;
 		plan.batch = tune.mainBatch;
+		plan.trTables = tune.fastT() ? 1u : 0u;
 		plan.upperNum = withLevel0 ? tune.mainUpperNum : 1u; plan.upperDen = withLevel0 ? tune.mainUpperDen : 1u;
 		unsigned long long items = 0; // at most: one material item per block, one regular, one transition
 		for (u32 l = 1; l < levels; ++l) items += (unsigned long long)p.levels[l].cap * (1u + (l < plan.fastEnd ? 1u : 0u) + (p.levels[l].hasTransitions ? 1u : 0u));
@@ -3727,6 +3753,7 @@ struct Backend {
 		plan.level0 = 1u;
 		const u32 slots = (u32)cus * tune.mainWgsPerCu;
 		plan.batch = q.start[1] > 2u * slots ? tune.mainBatch : 1u; // (few blocks: every one its own workgroup)
+		plan.trTables = tune.fastT() ? 1u : 0u;
 		plan.upperNum = tune.mainUpperNum; plan.upperDen = tune.mainUpperDen;
 		memcpy(plan.boxLo, q.lo, sizeof(plan.boxLo)); memcpy(plan.boxHi, q.hi, sizeof(plan.boxHi));
 		u32 items = q.start[1], upperVol = 0;
@@ -3977,8 +4004,8 @@ struct Backend {
 		// 1024: 0.117, 1536: 0.126, one workgroup per block: 0.109 - a workgroup's start costs about as much as its planes)
 		const u32 grid = std::min<u32>(cap, (u32)cus * 5);
 		const bool wide = (size_t)p.G.grid.n * p.G.grid.n * p.G.grid.n >= ((size_t)1 << 32) || tune.forceWide;
-		if (wide) hipLaunchKernelGGL(k_transition<true>, dim3(grid), dim3(WG), TR_TAB_LDS + sizeof(TrState), stream, dev(p), levels);
-		else hipLaunchKernelGGL(k_transition<false>, dim3(grid), dim3(WG), TR_TAB_LDS + sizeof(TrState), stream, dev(p), levels);
+		if (wide) hipLaunchKernelGGL(k_transition<true>, dim3(grid), dim3(WG), TR_TAB_LDS + sizeof(TrState), stream, dev(p), levels, tune.fastT() ? 1u : 0u);
+		else hipLaunchKernelGGL(k_transition<false>, dim3(grid), dim3(WG), TR_TAB_LDS + sizeof(TrState), stream, dev(p), levels, tune.fastT() ? 1u : 0u);
 		check(hipGetLastError(), "k_transition launch");
 	}
 };

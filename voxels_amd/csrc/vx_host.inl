@@ -11,6 +11,7 @@
 #include "tv_block.h"
 #include "tv_fast0.h"
 #include "tv_fast1.h"
+#include "tv_fastt.h"
 
 #include <algorithm>
 #include <atomic>
@@ -456,7 +457,7 @@ void fill_params(vx_ctx* c, ExecParams& p, u32 levels)
 
 void build_table_image(std::vector<u8>& img)
 {
-	img.assign(TAB_F0_BYTES, 0);
+	img.assign(TAB_FT_BYTES, 0);
 	memcpy(&img[TAB_REG_CLASS], TVT_REG_CLASS, 256);
 	memcpy(&img[TAB_REG_CELL], TVT_REG_CELL, 256);
 	memcpy(&img[TAB_TR_CLASS], TVT_TR_CLASS, 512);
@@ -496,6 +497,7 @@ void build_table_image(std::vector<u8>& img)
 	pack(TVT_TR_VERT, 512, TAB_TR_EDGE, TAB_TR_VERT);
 	static_assert((u32)TAB_F0_CASE == (u32)TAB_BYTES, "the fast-pass tables follow the image of tv_core.h");
 	f0_build_tables(img.data(), TVT_REG_CLASS, TVT_REG_CELL, TVT_REG_VERT, (const u16*)&img[TAB_REG_EDGE]);
+	trf_build_tables(img.data(), TVT_TR_CLASS, TVT_TR_CELL, TVT_TR_VERT);
 }
 
 // one pass of the device pipeline over the blocks listed in the level tables
@@ -736,12 +738,12 @@ int vx_ctx_create(int device_index, vx_ctx** out)
 	if (const char* e = getenv("VX_POOL_SLACK")) c->poolSlack = std::max<u32>(64u, (u32)atoll(e));
 	std::vector<u8> img;
 	build_table_image(img);
-	c->dTables = c->be.alloc(TAB_F0_BYTES);
+	c->dTables = c->be.alloc(TAB_FT_BYTES);
 	c->dLut = c->be.alloc(256 * 8);
 	c->dHeader = c->be.alloc((HDR_WORDS + HDR_PARTIALS) * 4); // header + the block-class partial sums of k_run_head (one word per workgroup)
 	c->headerSet[0] = c->dHeader;
 	c->headerSet[1] = c->be.alloc((HDR_WORDS + HDR_PARTIALS) * 4);
-	if (!c->dTables || !c->dLut || !c->dHeader || !c->headerSet[1] || !c->be.h2d(c->dTables, img.data(), TAB_F0_BYTES)) {
+	if (!c->dTables || !c->dLut || !c->dHeader || !c->headerSet[1] || !c->be.h2d(c->dTables, img.data(), TAB_FT_BYTES)) {
 		vx_ctx_destroy(c);
 		return VX_ERR_DEVICE;
 	}
@@ -2299,6 +2301,14 @@ int vx_stats(vx_ctx* c, uint32_t stats[20])
 	VX_ENTER(c);
 	if (!c || !c->haveSurface) return fail(c, VX_ERR_INVALID, "vx_stats: nothing polygonized yet");
 	memcpy(stats, c->stats, 80);
+	return VX_OK;
+}
+
+int vx_transition_path_counts(vx_ctx* c, uint32_t out[2])
+{
+	VX_ENTER(c);
+	if (!c || !out || !c->haveSurface) return fail(c, VX_ERR_INVALID, "vx_transition_path_counts: nothing polygonized yet");
+	out[0] = c->hdr[HDR_STATS + STAT_TR_PATHS]; out[1] = c->hdr[HDR_STATS + STAT_TR_PATHS + 1];
 	return VX_OK;
 }
 

@@ -3,7 +3,8 @@
 // material blocks their children's (mat_block, selfChild).  Included by vx_hip.hip
 // behind the passes whose per-block bodies it calls: f0_walk (table-driven regular cells of level-0 blocks, vx_fast0.inl),
 // mat_block (the material vote of one block of a level >= 1, vx_hip.hip), f1_block (the table-driven regular cells of one
-// block of a level 1..3, vx_fast1.inl), tr_block (the transition cells of one block, vx_hip.hip).
+// block of a level 1..3, vx_fast1.inl), tr_block (the transition cells of one block, vx_hip.hip, with the table-driven body
+// of vx_fastt.inl).
 //
 // The reference walks the levels one after the other (TransVoxelRun::Execute, src/TransVoxelImpl.cpp:492-531): the material
 // cache of a level-L cell is a vote over its eight children on level L-1 (:753-838), a block's regular and transition
@@ -52,6 +53,7 @@ struct MainPlan {
 	// but produce no meshes (another device produces those, libVoxels.so with VOXELS_DEVICES): no level-0 queue, regular and
 	// transition items only for the levels >= emitFrom
 	u32 emitFrom;
+	u32 trTables;   // 1: transition blocks take the table-driven body where they qualify (VX_FAST bit 2; vx_fastt.inl)
 };
 
 // DIRTY: the incremental run's form (TransVoxelRun::Execute with a Modification, src/TransVoxelImpl.cpp:429-465): the same two
@@ -158,14 +160,15 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 			if (tabKind != 2u) { TT = stage_transition_tables(tab, p.tables, (u32)tid); tabKind = 2u; }
 			RegBlockCtx b;
 			b.level = level; b.slot = slot;
-			tr_block<false, true>(p, b, coord, *(TrState*)state, TT, scanScratch, quietFaces, quietParity, smp, tid, false);
+			tr_block<false, true>(p, b, coord, *(TrState*)state, TT, scanScratch, quietFaces, quietParity, smp, tid, plan.trTables != 0u, wgStats + 2, false);
 		}
 	}
 	__syncthreads();
 	{
 		int tid = tid0;
 		asm volatile("" : "+v"(tid)); // (the address is formed here, not carried through the kernel)
-		if (tid < 20 && wgStats[tid]) atomicAdd(&p.G.stats[tid], wgStats[tid]);
+		// (no item of this kernel counts into the words 2 and 3: they hold the transition blocks by body, STAT_TR_PATHS)
+		if (tid < 20 && wgStats[tid]) atomicAdd(&p.G.stats[(tid == 2 || tid == 3) ? (int)STAT_TR_PATHS + tid - 2 : tid], wgStats[tid]);
 	}
 }
 
