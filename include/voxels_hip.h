@@ -52,7 +52,13 @@ typedef struct vx_block_info {
 typedef struct vx_exec_info {
 	uint32_t levels;            /* LOD levels produced (PolygonSurface::GetLevelsCount) */
 	uint32_t retries;           /* re-runs after growing the output pools */
-	float device_ms;            /* device time of the last run, HIP events on the context's stream */
+	float device_ms;            /* device time of the last run, always > 0.  A full run on the single-stream path (three launches;
+	                             * stage timing off): the device's constant 100 MHz clock, from the moment the first workgroup of
+	                             * the first kernel starts to the publication of the run's header by the last kernel - a few
+	                             * microseconds less than the interval between two HIP events around the same launches, which also
+	                             * holds the first kernel's dispatch and the rest of the last kernel after the publication.  Every
+	                             * other run (the chain of launches, stage timing, VX_HOST_TIMING, incremental runs): that pair of
+	                             * HIP events on the context's stream. */
 	uint64_t total_verts;       /* the vertex pool's cursor: vertices of all meshes (regular + transition, incl. blocks dropped as
 	                             * empty) PLUS the ranges a table-driven block of a level >= 1 had reserved when it turned out to
 	                             * hold a zero sample and was handed to the general pass (a handful of blocks per run; the
@@ -347,6 +353,11 @@ int vx_material_lut(vx_ctx* ctx, const uint8_t* lut /*256*6*/, const uint8_t* va
 /* ---- polygonization = TransVoxelRun::Execute (src/TransVoxelImpl.cpp:468-538) ------------------------ */
 /* num_levels = 0: all log2(n/16)+1 levels like the reference; otherwise only levels 0..num_levels-1 (the
  * "last level has no transitions" rule still uses the reference's level count). */
+/* When the call returns, the run's header (info, vx_stats) is complete and every mesh is in the pools; on the single-stream path
+ * the run's last kernel may still be writing the device block tables.  Whatever is queued on the context's stream afterwards is
+ * ordered behind it, another vx_polygonize included (which does not wait for the stream), and every other entry point of the
+ * context waits for it first.  Only work of the caller's own on ANOTHER stream that reads the block tables has to order itself
+ * behind the context's stream.  VX_SYNC_WAIT=1 (read when the context is created) makes every run wait for its stream. */
 int vx_polygonize(vx_ctx* ctx, uint32_t num_levels, vx_exec_info* info);
 /* The same run without the meshes of the levels below first_meshed_level - for a caller that gets those from other devices
  * (libVoxels.so with VOXELS_DEVICES = N: helper contexts polygonize the finer levels slab by slab) but needs everything a later

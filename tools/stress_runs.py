@@ -20,10 +20,27 @@ def signature(p, info):
     return (int(info.total_verts), int(info.total_indices), tuple(int(x) for x in info.active_blocks[:info.levels]), tuple(int(x) for x in p.stats()))
 
 
+def rss_mib():
+    with open("/proc/self/status") as f:
+        for line in f:
+            if line.startswith("VmRSS:"):
+                return int(line.split()[1]) / 1024.0
+    return 0.0
+
+
+# Back-to-back runs do not wait for their stream (a run returns when its header has arrived): a runtime that kept every command of
+# a stream nobody waits for would grow by at least the kernels' arguments, ~1 KiB per launch and three launches per run - more
+# than 100 MiB over 40 000 runs.  Growth beyond this many MiB during a loop fails the stress run.
+RSS_GROWTH_LIMIT_MIB = 32.0
+
+
 def stress(name, p, levels, runs):
     info = p.execute(levels)
     first = signature(p, info)
     d0 = digest.surface_digest(p.all_levels())
+    for _ in range(200):  # (the allocator's and the runtime's pools have their working size before memory is looked at)
+        p.execute(levels)
+    rss0 = rss_mib()
     t = time.perf_counter()
     for i in range(runs):
         info = p.execute(levels)
@@ -32,9 +49,11 @@ def stress(name, p, levels, runs):
             print("%s: run %d differs: %s vs %s" % (name, i, s, first))
             return False
     dt = time.perf_counter() - t
+    grown = rss_mib() - rss0
     ok = digest.digests_equal(digest.surface_digest(p.all_levels()), d0)
-    print("%s: %d runs, %.4f ms per run (counts and statistics read back every run), last digest %s the first" % (name, runs, dt / runs * 1e3, "equals" if ok else "DIFFERS FROM"))
-    return ok
+    print("%s: %d runs, %.4f ms per run (counts and statistics read back every run), last digest %s the first, resident memory %+.1f MiB over the loop"
+          % (name, runs, dt / runs * 1e3, "equals" if ok else "DIFFERS FROM", grown))
+    return ok and grown < RSS_GROWTH_LIMIT_MIB
 
 
 def main():

@@ -38,6 +38,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -52,6 +53,7 @@
 #include "vx_terrain_math.h"
 
 #define VX_BACKEND_NAME "hip:gfx950"
+#define VX_BACKEND_HEADER_WAIT 1 // this backend times a run by the device clock and lets the host wait for the header (vx_host.inl RunClock)
 
 namespace {
 using namespace tv;
@@ -153,6 +155,9 @@ __device__ __forceinline__ void store16_through(void* uniformBase, u32 byteOffse
 	v4u32 x = { v.x, v.y, v.z, v.w };
 	__builtin_amdgcn_raw_buffer_store_b128(x, rsrc, (int)byteOffset, 0, /* aux: sc1 */ 16);
 }
+// the constant 100 MHz clock (the same on every XCD), low word: differences are exact modulo 2^32 ticks = 42.9 s
+__device__ __forceinline__ u32 run_clock() { return (u32)wall_clock64(); }
+
 // -DVX_CONSERVATIVE_SYNC (libvoxels_hip_conservative.so, a test build of the same sources): the textbook form of the same
 // protocol - every producer wave releases at agent scope before the barrier, the flag is a release store, the poll an acquire
 // load, and every consumer wave acquires behind the barrier - so that nothing rests on which stores and loads were written
@@ -1034,10 +1039,13 @@ __global__ __launch_bounds__(WG) void k_reset(ExecParamsDev p, ResetRanges r)
 // (what k_classify + k_hierarchy do for a run whose classification is a pass of its own).  Not quiet means: the 17^3 samples
 // the block's cells read are not of one sign, so at least one cell is non-trivial - exactly the blocks k_classify finds
 // active.  Their bitmaps are then the business of whoever polygonizes them (k_main: f0_walk<.., SELF>, mat_block).
-__global__ __launch_bounds__(WG) void k_run_head(ExecParamsDev p, ResetRanges r, u32 allocate)
+// clockStart: where workgroup 0 leaves the 100 MHz clock as it starts - the start of the run's device_ms (include/voxels_hip.h);
+// nullptr: the run is timed by events.  A header word of the run's set, so only with r.header == nullptr (no reset in here).
+__global__ __launch_bounds__(WG) void k_run_head(ExecParamsDev p, ResetRanges r, u32 allocate, u32* clockStart)
 {
 	const LevelDesc& L = p.levels[0];
 	const u32 i = blockIdx.x * WG + threadIdx.x;
+	if (clockStart && i == 0) __hip_atomic_store(clockStart, run_clock(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (read by the publishing workgroup of k_tail, possibly on another XCD)
 	if (r.header) reset_words(r, i);
 	if (r.header && i < r.listWgs) r.listCounts[i] = 0;
 	const u32 rowsY = L.yb1 - L.yb0;
@@ -2524,12 +2532,39 @@ __global__ __launch_bounds__(LIST_WG) void k_list_count(ExecParamsDev p, ListPla
 // publish: the workgroup that finishes last copies the run's header (counters, totals, statistics; the block-class partial
 // sums behind it) into page-locked host memory - the host then needs no copy behind the run's last kernel (a blit kernel of
 // its own: ~3.5 us, and ~5.5 us until it starts), only the wait it does anyway.
+// The host may wait for the publication itself instead of the kernel's end (Backend::wait_published): the word `flagWord` of
+// the host copy is written last, by one lane, with the run's tag - after every other word left through write-through stores
+// that every storing wave waited for (the form of publish_done_through, at system scope: no fence, so no write-back of the
+// XCD's L2 - the list entries this launch just wrote sit there).  `clockWord` of the host copy receives the 100 MHz clock at the publication
+// (0: the header's own word), the end of device_ms; k_run_head stored its start into the header.
 struct HeaderPublish {
 	u32* done;         // counter of finished workgroups (a header word: zeroed with the run's counters)
 	u32* host;         // page-locked destination (nullptr: no publication)
 	const u32* dev;    // the header
 	u32 words;
+	u32 flagWord, flag; // the word of the host copy that says "published", and what it then holds (the run's tag, never 0)
+	u32 clockWord;
 };
+
+// every lane of the publishing workgroup
+__device__ __forceinline__ void publish_header_to_host(const HeaderPublish& pub, const u32 tid, const u32 lanes)
+{
+	const u32 now = run_clock();
+	for (u32 i = tid; i < pub.words; i += lanes) {
+		if (i == pub.flagWord) continue;
+		const u32 v = (pub.clockWord && i == pub.clockWord) ? now : TV_LOAD_THROUGH(pub.dev + i);
+		__hip_atomic_store(pub.host + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	}
+#if defined(VX_CONSERVATIVE_SYNC)
+	__threadfence_system();
+	__syncthreads();
+	if (tid == 0) __hip_atomic_store(pub.host + pub.flagWord, pub.flag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+#else
+	asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // every storing wave: its write-through stores have left
+	__syncthreads();
+	if (tid == 0) __hip_atomic_store(pub.host + pub.flagWord, pub.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+#endif
+}
 
 // (workgroup w of listWgs: a launch of its own, or the workgroups of k_tail behind the general passes)
 __device__ __forceinline__ void list_write_pass(const ExecParamsDev& p, const ListPlan& plan, u32 levels, const HeaderPublish& pub, const u32 w, const u32 listWgs, const bool countsThrough)
@@ -2590,7 +2625,7 @@ __device__ __forceinline__ void list_write_pass(const ExecParamsDev& p, const Li
 	}
 	if (pub.host && levelFinal) {
 		__syncthreads();
-		if (baseShared) for (u32 i = tid; i < pub.words; i += LIST_WG) pub.host[i] = TV_LOAD_THROUGH(pub.dev + i);
+		if (baseShared) publish_header_to_host(pub, tid, LIST_WG);
 	}
 	(void)listWgs;
 }
@@ -3108,7 +3143,7 @@ struct Backend {
 	int device = 0;
 	bool ok = true;
 	// launch geometry knobs, read from the environment once when the context is created (tuning aids)
-	// Runtime knobs (read once per context).  Seven in all with VX_POOL_SLACK and VX_HOST_TIMING (vx_host.inl); each selects a path
+	// Runtime knobs (read once per context).  Eight in all with VX_POOL_SLACK and VX_HOST_TIMING (vx_host.inl); each selects a path
 	// that production runs reach through their data - dense surfaces, grids beyond 1024^3, blocks with zero samples - so that the
 	// tests can drive those paths on small fixtures (tests/test_gpu_parity.py::test_hip_runtime_knobs_select_equivalent_paths).
 	struct Tuning {
@@ -3118,6 +3153,7 @@ struct Backend {
 		u32 upper = 1;       // VX_UPPER=0: the chain of launches (what dense surfaces run) instead of k_main
 		u32 selfHead = 1;    // VX_SELF_HEAD=0: a classification pass (k_classify, k_hierarchy) instead of k_run_head handing out the slots
 		u32 dirtyFused = 1;  // VX_DIRTY_FUSED=0: incremental runs as the chain of launches with work lists
+		u32 syncWait = 0;    // VX_SYNC_WAIT=1: a full run is waited for with hipStreamSynchronize where the default waits for its header (wait_published)
 		// fixed since round 6 (were environment variables while they were being measured; profiles/HISTORY.md has the sweeps)
 		static constexpr u32 classifyRowGroup = 4, regWgsPerCu = 20, f1WgsPerCu = 20, foldBlocks = 65536, upWgsPerCu = 5, mainWgsPerCu = 4, mainBatch = 2, mainUpperNum = 1, mainUpperDen = 4;
 		bool fast0() const { return (fast & 1u) != 0; }
@@ -3150,6 +3186,7 @@ struct Backend {
 		tune.upper = env_u32("VX_UPPER", 1);
 		tune.selfHead = env_u32("VX_SELF_HEAD", 1);
 		tune.dirtyFused = env_u32("VX_DIRTY_FUSED", 1);
+		tune.syncWait = env_u32("VX_SYNC_WAIT", 0);
 		hipDeviceProp_t prop;
 		if (hipGetDeviceProperties(&prop, device) == hipSuccess) cus = prop.multiProcessorCount;
 		if (!check(hipStreamCreateWithFlags(&ownStream, hipStreamNonBlocking), "hipStreamCreate")) { err = lastError; return false; }
@@ -3275,6 +3312,33 @@ struct Backend {
 	// (Polling the stream with hipStreamQuery instead was tried against the sporadic 80-95 ms stalls of DESIGN section 9: they also
 	// hit kernel launches and event records, with and without polling, and polling costs 5-10 us per call.)
 	bool sync_ok() { return check(hipStreamSynchronize(stream), "hipStreamSynchronize"); }
+	// The wait of a single-stream full run: for the word its publishing workgroup writes last into the page-locked header
+	// (HeaderPublish), not for the stream - the kernel's other workgroups, its end-of-kernel release and the runtime's wake-up
+	// of a sleeping thread all come after the one thing the caller needs.  The stream is asked (5-10 us per question, so rarely:
+	// not before twice the device time of this context's previous run has passed, then every 100 us; a context's first run asks at
+	// once) only to end the wait of a run that will never publish: a stream that is done, or broken, ends it, so the wait is
+	// bounded by the stream's own completion and needs no timeout of its own.
+	// 1: published; 0: the stream finished and the flag is not there; -1: the stream reports an error (lastError).
+	float prevRunMs = 0.f; // device_ms of this context's previous single-stream run (0: none yet)
+	bool flag_wait() const { return !tune.syncWait; }
+	int wait_published(const u32* flag, u32 value)
+	{
+		const auto t0 = std::chrono::steady_clock::now();
+		double askAt = 2e3 * (double)prevRunMs; // us
+		for (u32 spins = 0;; ++spins) {
+			if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == value) return 1;
+#if defined(__x86_64__) || defined(__i386__)
+			__builtin_ia32_pause();
+#endif
+			if (askAt > 0. && (spins & 63u) != 63u) continue; // (the clock every 64 looks)
+			const double us = (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count() * 1e-3;
+			if (us < askAt) continue;
+			const hipError_t e = hipStreamQuery(stream);
+			if (e == hipErrorNotReady) { askAt = us + 100.; continue; }
+			if (e != hipSuccess) { check(e, "hipStreamQuery"); return -1; }
+			return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == value ? 1 : 0;
+		}
+	}
 	bool d2h_async(void* d, const void* s, size_t bytes) { return check(hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(D2H)"); }
 	bool h2d_async(void* d, const void* s, size_t bytes) { return check(hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(H2D)"); } // (page-locked source)
 	// a copy that does not queue behind the context's streams (diagnostics while a run is in flight)
@@ -3325,6 +3389,13 @@ struct Backend {
 		return true;
 	}
 	void begin_timing() { (void)hipEventRecord(ev0, stream); }
+	// Device time without stream packets (single-stream full runs while stage timing is off): k_run_head's workgroup 0 leaves the
+	// 100 MHz clock in a header word (clockStart, set by the host per run; nullptr = the run is timed by the event pair), the
+	// publishing workgroup of the list pass puts the clock into the host copy of another (HeaderPublish::clockWord).
+	u32* clockStart = nullptr;
+	template <typename P>
+	bool clock_timing_applies(const P& p, u32 levels) const { return single_stream(p, levels) && !stageOn; }
+	static float clock_ms(u32 start, u32 end) { return (float)std::max<u32>(end - start, 1u) * 1e-5f; } // (positive: callers divide by it)
 	float end_timing_ms()
 	{
 		(void)hipEventRecord(ev1, stream);
@@ -3487,7 +3558,7 @@ struct Backend {
 			headWorkgroups = 0; // (no partial sums behind the header: see k_run_head)
 			// (workgroups are 8 x 8 x 4 boxes of blocks at aligned places that cover the block range)
 			const u32 boxes = ((L.cnt + 7u) >> 3) * (((L.yb1 + 7u) >> 3) - (L.yb0 >> 3)) * (((L.zb1 + 3u) >> 2) - (L.zb0 >> 2));
-			hipLaunchKernelGGL(k_run_head, dim3(boxes), dim3(WG), 0, stream, dev(p), r, 1u);
+			hipLaunchKernelGGL(k_run_head, dim3(boxes), dim3(WG), 0, stream, dev(p), r, 1u, clockStart);
 			check(hipGetLastError(), "k_run_head launch");
 			stage_mark(1);
 			return;
@@ -3497,7 +3568,7 @@ struct Backend {
 			pendingReset.header = nullptr;
 			const u32 lanes = std::max<u32>(L.cnt * rowsY * (L.zb1 - L.zb0), r.header ? std::max<u32>((r.start[MAX_LEVELS] + 3) / 4, r.listWgs) : 0u);
 			headWorkgroups = (lanes + WG - 1) / WG;
-			hipLaunchKernelGGL(k_run_head, dim3(headWorkgroups), dim3(WG), 0, stream, dev(p), r, 0u);
+			hipLaunchKernelGGL(k_run_head, dim3(headWorkgroups), dim3(WG), 0, stream, dev(p), r, 0u, (u32*)nullptr);
 		}
 		const u32 rows = rowsY * (L.zb1 - L.zb0);
 		u32 rowGroup = 0; // 0 = no remap
@@ -3965,6 +4036,8 @@ struct Backend {
 		publish.host = hostDst; publish.dev = devHeader; publish.words = words; publish.done = doneCounter;
 		return true;
 	}
+	// ... and, behind it: the word of the host copy that is written last, what it then holds, the word that receives the clock
+	void publish_tagged(u32 flagWord, u32 flag, u32 clockWord) { publish.flagWord = flagWord; publish.flag = flag; publish.clockWord = clockWord; }
 	template <typename P>
 	bool run_block_lists(const P& p, const ListPlan& plan, u32 levels)
 	{

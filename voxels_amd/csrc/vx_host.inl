@@ -47,7 +47,7 @@ typedef ListedBlock EmittedBlock;
 
 // largest grid edge: 2048 = 8 LOD levels (MAX_LEVELS) and 32-bit element offsets inside a block neighbourhood
 enum { VX_MAX_GRID = 2048 };
-enum { HDR_WORDS = 576, HDR_LISTS = 8, HDR_CURSORS = 32, HDR_STATS = 128, HDR_WORK = 160, HDR_LARGE = 176, HDR_SLOW = 224, HDR_UPPER = 256, HDR_GIVEUP = 288, HDR_PUBLISHED = 289 /* workgroups of the list pass that are done */, HDR_L0HEAD = 320 /* the head of k_main's level-0 queue, one for the chip */, HDR_PARTIALS = 32768 }; // counters spread over 128-byte lines
+enum { HDR_WORDS = 576, HDR_LISTS = 8, HDR_CURSORS = 32, HDR_STATS = 128, HDR_WORK = 160, HDR_LARGE = 176, HDR_SLOW = 224, HDR_UPPER = 256, HDR_GIVEUP = 288, HDR_PUBLISHED = 289 /* workgroups of the list pass that are done; in the host copy: the tag of the run whose header this is */, HDR_L0HEAD = 320 /* the head of k_main's level-0 queue, one for the chip */, HDR_CLOCK0 = 352, HDR_CLOCK1 = 384 /* the 100 MHz clock at the start of k_run_head / at the publication of the header */, HDR_PARTIALS = 32768 }; // counters spread over 128-byte lines
 
 } // namespace
 
@@ -136,6 +136,11 @@ struct vx_ctx {
 	u32 runEpoch = 0;           // tag of the current full run in LevelDesc::matDone (Globals::epoch)
 	u32 poolSlack = 1u << 16;   // VX_POOL_SLACK (read once at context creation; tests): the vertices of headroom the pool rules add - smallest pool, packing threshold, room for edits (indices: four times as many)
 	bool hostTiming = false;    // VX_HOST_TIMING (read once at context creation): print where a vx_polygonize call spends host time
+	// vx_polygonize returned when the run's header arrived (Backend::wait_published): the last kernel may still be running.  Whatever
+	// comes next on the context's stream is ordered behind it; every entry point other than vx_polygonize waits for it first
+	// (VX_ENTER -> settle_run), because it may free, reallocate or read on the host what the run still touches.
+	bool runInFlight = false;
+	u32 unsettledRuns = 0;      // full runs since the stream was last waited for (see SETTLE_EVERY)
 	// ray casts (vx_ray.inl): every full run, incremental run and pool compaction counts up meshEpoch (the pools may come back at
 	// the same address, so pointers say nothing); fullRunEpoch = its value after the last full run (the block tables' counts are
 	// then the run's device header words)
@@ -157,8 +162,42 @@ struct vx_ctx {
 	void (*smoothFree)(vx_ctx*) = nullptr;
 };
 
+// What only a backend with a device clock and a header the host can wait on offers (VX_BACKEND_HEADER_WAIT, defined by the
+// including file: the HIP backend).  Without it - the CPU emulation, whose runs are complete when they return and which
+// reports no device time - every run is timed and waited for through begin_timing / end_timing_record / sync_ok.
+struct RunClock {
+#if defined(VX_BACKEND_HEADER_WAIT)
+	template <typename P> static bool applies(const Backend& be, const P& p, u32 levels) { return be.clock_timing_applies(p, levels); }
+	static void start_word(Backend& be, u32* word) { be.clockStart = word; }
+	static void tag(Backend& be, u32 flagWord, u32 flag, u32 clockWord) { be.publish_tagged(flagWord, flag, clockWord); }
+	static bool waits_for_header(const Backend& be) { return be.flag_wait(); }
+	static int wait(Backend& be, const u32* flag, u32 value) { return be.wait_published(flag, value); }
+	static float ms(Backend& be, u32 start, u32 end) { return be.prevRunMs = Backend::clock_ms(start, end); }
+#else
+	template <typename P> static bool applies(const Backend&, const P&, u32) { return false; }
+	static void start_word(Backend&, u32*) {}
+	static void tag(Backend&, u32, u32, u32) {}
+	static bool waits_for_header(const Backend&) { return false; }
+	static int wait(Backend&, const u32*, u32) { return 0; }
+	static float ms(Backend&, u32, u32) { return 0.f; }
+#endif
+};
+
 // every entry point makes the context's device the calling thread's current device (the HIP current device is per thread)
-#define VX_ENTER(c) do { if (c) (c)->be.make_current(); } while (0)
+// ... and, except vx_polygonize (which settles only where it has to), waits for a run that is still in flight
+static inline void settle_run(vx_ctx* c)
+{
+	if (!c->runInFlight) return;
+	c->be.sync();
+	c->runInFlight = false;
+	c->unsettledRuns = 0;
+}
+#define VX_ENTER_RUN(c) do { if (c) (c)->be.make_current(); } while (0)
+#define VX_ENTER(c) do { if (c) { (c)->be.make_current(); settle_run(c); } } while (0)
+// A stream that is never waited for keeps every command it was given (the runtime releases them when a wait or an event
+// completes): back-to-back runs wait for the stream once in so many - behind the header's arrival, when the kernel is all but
+// done - which bounds what is kept at no measurable cost per run.
+enum { SETTLE_EVERY = 64 };
 
 namespace {
 
@@ -1454,7 +1493,10 @@ int vx_polygonize(vx_ctx* c, uint32_t num_levels, vx_exec_info* info) { return v
 
 int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_level, vx_exec_info* info)
 {
-	VX_ENTER(c);
+	// (a run behind a run: not waited for - every other entry point has settled, so the grid, the mirrors and the tables are
+	// what the run in flight works on; a changed grid settles all the same, before anything is rebuilt or freed)
+	VX_ENTER_RUN(c);
+	if (c && (c->bricksStale || !c->vertCap)) settle_run(c);
 	if (!c || !c->n || !c->dDist) return fail(c, VX_ERR_INVALID, "vx_polygonize: no grid resident (call vx_grid_upload / vx_grid_attach first)");
 	if (!ensure_level_tables(c)) return fail(c, VX_ERR_DEVICE, "vx_polygonize: level table allocation failed: " + c->be.error());
 	++c->meshEpoch;
@@ -1507,7 +1549,12 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 		// a partial run (first_meshed_level > 0) exists on the single-stream path only; anything else meshes every level and says so
 		emitFrom = (first_meshed_level && c->be.partial_applies(p, levels)) ? std::min<u32>(first_meshed_level, levels) : 0u;
 		c->be.emitFrom = emitFrom;
-		c->be.begin_timing();
+		// device time: two clock words of the header on the single-stream path; the event pair on the chain of launches, with
+		// stage timing and under VX_HOST_TIMING (a recorded event is a packet of its own in the stream: ~8 us before the next kernel)
+		const bool byClock = !hostTiming && RunClock::applies(c->be, p, levels);
+		if (!byClock) settle_run(c); // (only a single-stream run follows a run in flight unwaited)
+		RunClock::start_word(c->be, byClock ? (u32*)c->dHeader + HDR_CLOCK0 : nullptr);
+		if (!byClock) c->be.begin_timing();
 		c->be.stage_mark(0);
 		c->be.tailDone = (u32*)c->dHeader + HDR_PUBLISHED + 1; // (k_tail's count of finished general workgroups)
 		c->be.run_reset(p, levels, (u32*)c->dHeader, HDR_WORDS, (u32*)c->dListCounts, c->listWgs, clean); // header = 0, slot maps = -1, list counts = 0
@@ -1541,21 +1588,36 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 			if (!c->hdrPinned) c->hdrPinned = (u32*)c->be.alloc_pinned((HDR_WORDS + HDR_PARTIALS) * 4);
 			if (!c->hdrPinned) { c->be.sync(); c->be.end_overlapped(); return fail(c, VX_ERR_DEVICE, "vx_polygonize: pinned allocation failed"); }
 			partials = std::min<u32>(c->be.head_partials(), (u32)HDR_PARTIALS);
+			// (the run before has published, or was waited for: nobody else writes this word now.  Its value when the header has
+			// arrived is this attempt's tag, which is not 0 and not the tag of the attempt before.)
 			c->hdrPinned[HDR_PUBLISHED] = 0;
 			published = c->be.lists_publish_header(c->hdrPinned, (const u32*)c->dHeader, HDR_WORDS + partials, (u32*)c->dHeader + HDR_PUBLISHED);
+			RunClock::tag(c->be, HDR_PUBLISHED, c->runEpoch, byClock ? (u32)HDR_CLOCK1 : 0u);
 			published = c->be.run_block_lists(p, plan, levels) && published;
 			c->otherSetClean = c->be.tailCleaned;
 			c->be.stage_mark(7);
 		}
-		c->be.end_timing_record();
+		if (!byClock) c->be.end_timing_record();
+		RunClock::start_word(c->be, nullptr);
+		if (byClock && !published) { c->be.sync(); c->be.end_overlapped(); return fail(c, VX_ERR_DEVICE, "vx_polygonize: a single-stream run without a published header (internal error)"); }
 		bool okRun = published || c->be.d2h_async(c->hdrPinned, c->dHeader, (HDR_WORDS + partials) * 4); // (one host wait per run either way)
 		t1 = tNow();
-		okRun = okRun && c->be.sync_ok();
+		if (okRun && byClock && RunClock::waits_for_header(c->be)) {
+			// the wait is for the header, not for the stream (Backend::wait_published): k_tail may still be running when this returns
+			const int arrived = RunClock::wait(c->be, c->hdrPinned + HDR_PUBLISHED, c->runEpoch);
+			okRun = arrived >= 0;
+			c->runInFlight = arrived > 0;
+			if (c->runInFlight && ++c->unsettledRuns >= (u32)SETTLE_EVERY) { okRun = c->be.sync_ok(); c->runInFlight = false; c->unsettledRuns = 0; } // (SETTLE_EVERY)
+		} else {
+			okRun = okRun && c->be.sync_ok();
+			c->runInFlight = false;
+			c->unsettledRuns = 0;
+		}
 		c->be.end_overlapped(); // (the tail of an overlapped run was queued on a side stream)
 		t2 = tNow();
 		if (!okRun) return fail(c, VX_ERR_DEVICE, "vx_polygonize: device run failed: " + c->be.error());
-		ms = c->be.elapsed_ms();
-		if (published && c->hdrPinned[HDR_PUBLISHED] == 0) return fail(c, VX_ERR_DEVICE, "vx_polygonize: the run's header did not arrive (internal error)");
+		if (published && __atomic_load_n(c->hdrPinned + HDR_PUBLISHED, __ATOMIC_ACQUIRE) != c->runEpoch) return fail(c, VX_ERR_DEVICE, "vx_polygonize: the run's header did not arrive (internal error)");
+		ms = byClock ? RunClock::ms(c->be, c->hdrPinned[HDR_CLOCK0], c->hdrPinned[HDR_CLOCK1]) : c->be.elapsed_ms();
 		memcpy(c->hdr, c->hdrPinned, HDR_WORDS * 4);
 		if (partials) { // the block-class statistics arrive as per-workgroup partial sums behind the header (k_run_head)
 			u32 readers = 0, calculated = 0;
@@ -1569,6 +1631,7 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 		if (c->hdr[HDR_LARGE] && !c->be.largeClass) { c->be.largeClass = true; continue; } // blocks of the large class showed up: once more, with it
 		if (!overflow) break;
 		if (++retries > 3) return fail(c, VX_ERR_OVERFLOW, "vx_polygonize: output pools keep overflowing");
+		settle_run(c); // (the pools are freed)
 		if (!ensure_pools(c, usedV + usedV / 8 + 1024, usedI + usedI / 8 + 4096)) return fail(c, VX_ERR_OVERFLOW, "vx_polygonize: cannot grow output pools");
 	}
 	c->be.emitFrom = 0;
@@ -2298,7 +2361,7 @@ int vx_stage_times(vx_ctx* c, float ms[8]) /* reset, classify, hierarchy, materi
 
 int vx_stats(vx_ctx* c, uint32_t stats[20])
 {
-	VX_ENTER(c);
+	VX_ENTER_RUN(c); // (the host's copy of the header: nothing a run in flight touches)
 	if (!c || !c->haveSurface) return fail(c, VX_ERR_INVALID, "vx_stats: nothing polygonized yet");
 	memcpy(stats, c->stats, 80);
 	return VX_OK;
@@ -2306,7 +2369,7 @@ int vx_stats(vx_ctx* c, uint32_t stats[20])
 
 int vx_transition_path_counts(vx_ctx* c, uint32_t out[2])
 {
-	VX_ENTER(c);
+	VX_ENTER_RUN(c);
 	if (!c || !out || !c->haveSurface) return fail(c, VX_ERR_INVALID, "vx_transition_path_counts: nothing polygonized yet");
 	out[0] = c->hdr[HDR_STATS + STAT_TR_PATHS]; out[1] = c->hdr[HDR_STATS + STAT_TR_PATHS + 1];
 	return VX_OK;
