@@ -139,6 +139,18 @@ int vx_grid_upload_slab_y(vx_ctx* ctx, uint32_t n, uint32_t y_begin, uint32_t y_
  * memory the library does not own).  The mirrors are rebuilt by the next polygonization; the emptiness flags stay the
  * caller's business, as with vx_grid_attach. */
 int vx_grid_invalidate(vx_ctx* ctx);
+/* One entry of the cell map, a mirror the library keeps with the others: the 4096-bit bitmap of the
+ * non-trivial cells of level-0 block (bx, by, bz) - bit x | y << 4 | z << 8 of out[128], i.e. the 16-bit row (z << 4) | y - and
+ * its population count.  A cell is non-trivial unless its eight corner samples agree in sign; a zero counts as >= 0,
+ * coordinates are clamped to the grid; the BF_Empty flags play no part.  Full runs on the single-stream path read the map
+ * instead of forming bitmaps; it is rebuilt by the first such run after the grid changed - and by this call, which brings it
+ * up to date if it is stale and copies one entry.  A block whose samples and the neighbour samples its cells reach are of one
+ * sign returns zeros and count 0.  Either output may be NULL.  Bringing the map up to date includes the other mirrors: on a
+ * grid that changed as a whole (upload, attach, vx_grid_invalidate) this call pays their rebuild, and the next
+ * vx_polygonize reports a mirror_ms without it.  VX_ERR_INVALID for a block outside the context's range and
+ * for a context that keeps no map: VX_CELLMAP=0 or a knob that rules out the single-stream path (read when the context is
+ * created), a grid beyond 1024^3, or a backend without mirrors.  No reference counterpart. */
+int vx_grid_cell_map(vx_ctx* ctx, uint32_t bx, uint32_t by, uint32_t bz, uint32_t out[128], uint32_t* count);
 /* Forget what earlier runs of this context learned about ITS surfaces - which capacity classes to launch, how many blocks the
  * general passes take over, how many upper-queue items a run has: the next run starts from the conservative defaults of a new
  * context (all capacity classes launched).  For a context that is handed to another owner with another grid (libVoxels.so:

@@ -231,6 +231,10 @@ class HipLibrary:
         if self.has_islands:
             lib.vx_grid_islands.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp]
             lib.vx_grid_islands.restype = C.c_int
+        # the cell map's read-back: libraries that keep the map
+        self.has_cell_map = hasattr(lib, "vx_grid_cell_map")
+        if self.has_cell_map:
+            lib.vx_grid_cell_map.argtypes = [vp, u32, u32, u32, vp, vp]
         # smoothing: HIP builds only, likewise
         self.has_smooth = hasattr(lib, "vx_grid_smooth")
         if self.has_smooth:
@@ -546,6 +550,16 @@ class Polygonizer:
         """The attached tensors were rewritten in place by the caller: the library's mirrors of them are rebuilt by the
         next execute().  Without this call (or a new attach) a run after an in-place edit polygonizes the OLD contents."""
         self._check(self._lib.vx_grid_invalidate(self._h), "vx_grid_invalidate")
+
+    def cell_map(self, bx, by, bz):
+        """vx_grid_cell_map: (128 uint32 words, count) - the bitmap of the non-trivial cells of level-0 block (bx, by, bz), bit
+        x | y << 4 | z << 8, from the cell map the library keeps with its mirrors (brought up to date first if it is stale)."""
+        if not self._L.has_cell_map:
+            raise VoxelsHipError("this library has no vx_grid_cell_map")
+        out = np.zeros(128, np.uint32)
+        count = C.c_uint32()
+        self._check(self._lib.vx_grid_cell_map(self._h, int(bx), int(by), int(bz), _ptr(out), C.byref(count)), "vx_grid_cell_map")
+        return out, int(count.value)
 
     def forget_hints(self):
         """What earlier runs taught this context about its surfaces (capacity classes, launch sizes) is forgotten: the next run

@@ -36,7 +36,7 @@ def build_hip(force=False, verbose=True):
     # wrong vertices now and then).  VX_ALLOW_SCRATCH=1 lifts the check for experiments.
     bad = [(k, v["ScratchSize"]) for k, v in table.items() if v.get("ScratchSize", 0)]
     # the gate must not pass because the remark format changed and nothing was parsed
-    missing = [k for k in ("k_regular0", "k_regular", "k_transition", "k_classify", "k_material", "k_main", "k_tail", "k_run_head", "k_dirty_head", "k_dirty_tail",
+    missing = [k for k in ("k_regular0", "k_regular", "k_transition", "k_classify", "k_material", "k_main", "k_tail", "k_run_head", "k_cell_map", "k_dirty_head", "k_dirty_tail",
                            "k_spherecast", "k_closest_point", "k_brush_apply",
                            "k_isl_local", "k_isl_merge", "k_isl_flatten", "k_isl_scan", "k_isl_roots", "k_isl_stats", "k_isl_mark", "k_isl_compact", "k_isl_remove",
                            "k_smooth_eval", "k_smooth_commit", "k_smooth_results")

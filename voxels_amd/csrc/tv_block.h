@@ -155,6 +155,10 @@ struct Globals {
 	// scratch, rebuilt by every full run from emptyFlags + one sample per empty block (level-0 blocks, [cnt0^3]):
 	u8* blockClass;                   // BC_* bits: what the classify pass may assume without reading the block
 	const u16* blockSign;             // per level-0 block, kept with the grid's mirrors: eight 2-bit sign summaries (MirrorState)
+	// full single-stream runs with the cell map (MirrorState::cellMap; nullptr in every other run): k_run_head takes a block's cell
+	// count from it, k_main's level-0 walk and level-1 material blocks its bitmap - nobody forms one
+	const u32* cellMap;               // [cnt0^3][128]
+	const u16* cellCount;             // [cnt0^3]
 	PyramidLevel pyr[PYRAMID_LEVELS]; // [1..]: lattice copies of the distance field for the coarser levels (GPU backend)
 	XPlanes xp[XPLANE_LEVELS];        // yz-planes of the lattices 0..2 at every 32nd x (the x faces of the transition pass)
 	// full runs: blocks the fast regular passes (tv_fast0.h, tv_fast1.h) hand on to the general pass (a zero sample, a LOD
@@ -188,6 +192,14 @@ struct MirrorState {
 	XPlanes xp[XPLANE_LEVELS];
 	u16* blockSign;                 // per level-0 block: field f = dx | dy << 1 | dz << 2 (2 bits each) summarises the voxels with x = 0 (dx), y = 0 (dy), z = 0 (dz): 1 = all >= 0, 2 = all < 0, 0 = mixed or not all resident
 	int yBegin, yEnd, zBegin, zEnd; // the rank's own rows / planes
+	// The cell map: the non-trivial-cell bitmap of every level-0 block of the rank's range by block COORDINATE, in the bit order of
+	// LevelDesc::ntBits (bit x | y << 4 | z << 8: the 16-bit row (z << 4) | y), and its population count.  A function of the
+	// distance samples alone (a cell is non-trivial unless its eight corner samples agree in sign, a zero counting as >= 0,
+	// coordinates clamped to the grid), independent of the BF_Empty flags.  Written by k_cell_map over the whole range whenever
+	// a byte of the distance mirror or a blockSign entry has changed since (vx_ctx::cellMapStale, ensure_cell_map); a block its
+	// blockSign fields prove quiet has cellCount 0 and map words nobody may read.  nullptr: the context keeps none.
+	u32* cellMap;                   // [cnt0^3][128]
+	u16* cellCount;                 // [cnt0^3]
 };
 enum { BC_SKIPPED = 1, BC_QUIET = 2, BC_NEGATIVE = 4 };
 

@@ -4,7 +4,8 @@
 // distances, 17^3 materials + blends and bitmap are requested into registers while the current block emits.  A block in whose staged samples a lane finds a zero byte is appended to Globals::slowItems[0] and left to
 // k_regular0<.., 2>, launched right behind on the same stream (or to the first workgroups of k_tail).  f0_walk is the body:
 // k_regular0_fast strides over all slots, k_main walks batches of consecutive slots taken from its queue - and there,
-// where no classification pass ran, a block forms its own non-trivial bitmap first (SELF: f0_self_bits, one barrier more).
+// where no classification pass ran, a block takes its non-trivial bitmap from the cell map by its coordinate (MAP:
+// Globals::cellMap, kept with the grid's mirrors) or, without the map, forms it first (SELF: f0_self_bits, one barrier more).
 //
 // Per block: deposit (+ zero test) | popcount prefix + compact cell list | cells: table-driven, no loop over table
 // vertices, wave-contiguous ranges, DPP scans | bases + pool reservations + vertex / triangle descriptors | one lane =
@@ -72,14 +73,16 @@ __device__ __forceinline__ int f0_row_part(int r, int lo, int hi, int brickStrid
 	return q * brickStride + (isZ ? (((l >> 1) << 9) | ((l & 1) << 6)) : (((l >> 2) << 7) | ((l & 3) << 4)));
 }
 
-template <bool SELF = false>
+template <bool SELF = false, bool MAP = false>
 __device__ __forceinline__ void f0_request(const GridView& g, const LevelDesc& L, const R0Block& b, F0Prefetch& pf)
 {
+	static_assert(!(SELF && MAP), "a block forms its bitmap or reads it");
 	const int tid = f0_opaque_tid();
 	const int n = g.n, cnt = (int)L.cnt;
 	// every lane loads (indices clamped into range): a conditional load with a default value makes the compiler wait for
 	// the data right behind the load, and these requests must stay in flight
-	if (!SELF) pf.bits = L.ntBits[(size_t)b.slot * 128 + (tid & 127)];
+	if (MAP) pf.bits = kernarg_params().G.cellMap[(size_t)b.coord * 128 + (tid & 127)];
+	else if (!SELF) pf.bits = L.ntBits[(size_t)b.slot * 128 + (tid & 127)];
 	const int brickRow = (n >> 4) * BRICK_BYTES, brickPlane = g.bRowsY * brickRow; // next block along y / z
 	const size_t own = brick_base(g, (int)b.bx, (int)b.by, (int)b.bz);
 	const bool firstX = b.bx == 0, lastX = (int)b.bx + 1 == cnt;
@@ -120,13 +123,20 @@ __device__ __forceinline__ void f0_request(const GridView& g, const LevelDesc& L
 // zero there sends a block to the general pass without need, which costs time, never correctness.)
 // SELF: nobody classified the block; the sign masks of its 19 x 19 sample rows (bit i = sample x = i, 0..16) are left in LDS
 // (on top of the vertex descriptors, which are written two barriers later) for f0_self_bits.
-template <bool SELF = false, typename ST>
+// MAP: the bitmap came from the cell map; it is also stored to the block's slot (bitmap and consistency bits), where the
+// passes behind this one - the general pass, incremental runs, the accessors - look for it.
+template <bool SELF = false, bool MAP = false, typename ST>
 __device__ __forceinline__ u32 f0_deposit(ST& st, const LevelDesc& L, const R0Block& b, const F0Prefetch& pf)
 {
 	const int tid = f0_opaque_tid();
 	const bool firstX = b.bx == 0, lastX = b.bx + 1 == L.cnt;
 	u32 zero = 0;
-	if (!SELF) { if (tid < 128) st.ntBits[tid] = pf.bits; }
+	if (!SELF) {
+		if (tid < 128) {
+			st.ntBits[tid] = pf.bits;
+			if (MAP) { L.ntBits[(size_t)b.slot * 128 + tid] = pf.bits; L.consBits[(size_t)b.slot * 128 + tid] = pf.bits; }
+		}
+	}
 	else if (tid == 0) st.zero = 0; // (the block's count of non-trivial cells is summed up here)
 	{
 		const int jj = tid % 19, group = tid / 19;
@@ -201,7 +211,7 @@ __device__ __forceinline__ R0Candidate f0_peek(const ExecParamsDev& p, const Lev
 	return c;
 }
 
-template <int CAP, bool REMAP, bool SELF = false>
+template <int CAP, bool REMAP, bool SELF = false, bool MAP = false>
 __device__ __forceinline__ bool f0_next(const ExecParamsDev& p, const LevelDesc& L, u32 total, u32 lo, u32 stride, u32 limit, u32& it, R0Candidate c, R0Block& b)
 {
 	for (;;) {
@@ -211,6 +221,17 @@ __device__ __forceinline__ bool f0_next(const ExecParamsDev& p, const LevelDesc&
 			((u16*)(L.ntBits + (size_t)slot * 128))[threadIdx.x] = 0;
 			((u16*)(L.consBits + (size_t)slot * 128))[threadIdx.x] = 0;
 			if (threadIdx.x == 0) L.ntCount[slot] = 0;
+		}
+		if (MAP && r0_uniform(c.valid)) {
+			// a block this walk leaves alone - skipped by the emptiness rule or without cells (zeros; its empty record follows in
+			// r0_accept), or beyond this capacity class (few: the host repeats the run) - still gets its slot's bitmaps here
+			const u32 slot = r0_uniform(c.slot), ntc = r0_uniform(c.ntc), skip = r0_uniform(c.skip), coord = r0_uniform(c.coord);
+			if ((skip || ntc == 0 || ntc > (u32)CAP) && threadIdx.x < 128) {
+				u32 w = 0;
+				if (!skip && ntc) w = p.G.cellMap[(size_t)coord * 128 + threadIdx.x];
+				L.ntBits[(size_t)slot * 128 + threadIdx.x] = w;
+				L.consBits[(size_t)slot * 128 + threadIdx.x] = w;
+			}
 		}
 		if (r0_accept<CAP>(L, lo, c, b)) return true;
 		it += stride;
@@ -223,7 +244,7 @@ __device__ __forceinline__ bool f0_next(const ExecParamsDev& p, const LevelDesc&
 // `cur` writes its output.  Leaves the LDS state free behind a barrier-less tail (callers meet before they reuse it).
 // The parameters are kernel argument 0, read through kernarg_params(): every caller is a __global__ whose first parameter is
 // the unmodified ExecParamsDev.
-template <int CAP, bool REMAP, bool SELF = false>
+template <int CAP, bool REMAP, bool SELF = false, bool MAP = false>
 __device__ __forceinline__ void f0_walk(const F0Tables& T, Fast0State<CAP>& st, u32* wgStats, u32* zeroFlag, u32& parity,
                                         u32 total, u32 lo, u32 first, u32 stride, u32 limit, const int tid)
 {
@@ -234,17 +255,17 @@ __device__ __forceinline__ void f0_walk(const F0Tables& T, Fast0State<CAP>& st, 
 	R0Block cur, nxt;
 	F0Prefetch pf;
 	// as in k_regular0: `cur` has its inputs requested, `nxt` is accepted and gets them requested while `cur` writes its output
-	bool have = f0_next<CAP, REMAP, SELF>(p, L, total, lo, stride, limit, it, f0_peek<REMAP>(p, L, total, limit, it), cur);
-	if (have) f0_request<SELF>(g, L, cur, pf);
+	bool have = f0_next<CAP, REMAP, SELF, MAP>(p, L, total, lo, stride, limit, it, f0_peek<REMAP>(p, L, total, limit, it), cur);
+	if (have) f0_request<SELF, MAP>(g, L, cur, pf);
 	it += stride;
-	bool haveNext = have && f0_next<CAP, REMAP, SELF>(p, L, total, lo, stride, limit, it, f0_peek<REMAP>(p, L, total, limit, it), nxt);
+	bool haveNext = have && f0_next<CAP, REMAP, SELF, MAP>(p, L, total, lo, stride, limit, it, f0_peek<REMAP>(p, L, total, limit, it), nxt);
 	while (have) {
 		F0_PARAMS();
 		const u32 candIt = it + stride;
 		R0Candidate cand;
 		__syncthreads(); // the previous block is done with the LDS state (and the tables are staged)
 		{
-			const u32 z = f0_deposit<SELF>(st, L, cur, pf);
+			const u32 z = f0_deposit<SELF, MAP>(st, L, cur, pf);
 			if (__ballot(z != 0) && (tid & 63) == 0) zeroFlag[parity] = 1;
 			if (tid == 0) zeroFlag[parity ^ 1u] = 0; // last read behind the previous block's second barrier
 		}
@@ -361,7 +382,7 @@ __device__ __forceinline__ void f0_walk(const F0Tables& T, Fast0State<CAP>& st, 
 					PolyVertex* vOut = p.P.verts + r0_uniform(st.vOff) + cv;
 					u32* iOut = p.P.idx + r0_uniform(st.iOff) + ct * 3u;
 					for (u32 base = 0; base < vEnd || base < tEnd; base += WG) {
-						if (!requested) { if (haveNext) f0_request<SELF>(g, L, nxt, pf); cand = f0_peek<REMAP>(p, L, total, limit, candIt); requested = true; }
+						if (!requested) { if (haveNext) f0_request<SELF, MAP>(g, L, nxt, pf); cand = f0_peek<REMAP>(p, L, total, limit, candIt); requested = true; }
 						const u32 j = base + (u32)tid;
 						if (j < vEnd) {
 							const u32 desc = st.vdesc[j], c = desc & 0xFFFu;
@@ -393,11 +414,11 @@ __device__ __forceinline__ void f0_walk(const F0Tables& T, Fast0State<CAP>& st, 
 			// a zero sample: the general pass takes the block
 			p.G.slowItems[0][atomicAdd(&p.G.slowCount[0], 1u)] = cur.slot;
 		}
-		if (!requested) { if (haveNext) f0_request<SELF>(g, L, nxt, pf); cand = f0_peek<REMAP>(p, L, total, limit, candIt); }
+		if (!requested) { if (haveNext) f0_request<SELF, MAP>(g, L, nxt, pf); cand = f0_peek<REMAP>(p, L, total, limit, candIt); }
 		cur = nxt;
 		have = haveNext;
 		it = candIt;
-		haveNext = have && f0_next<CAP, REMAP, SELF>(p, L, total, lo, stride, limit, it, cand, nxt);
+		haveNext = have && f0_next<CAP, REMAP, SELF, MAP>(p, L, total, lo, stride, limit, it, cand, nxt);
 	}
 }
 

@@ -53,6 +53,7 @@
 #include "vx_terrain_math.h"
 
 #define VX_BACKEND_NAME "hip:gfx950"
+#define VX_BACKEND_CELL_MAP 1    // this backend keeps the cell map (MirrorState::cellMap; vx_host.inl ensure_cell_map, vx_grid_cell_map)
 #define VX_BACKEND_HEADER_WAIT 1 // this backend times a run by the device clock and lets the host wait for the header (vx_host.inl RunClock)
 
 namespace {
@@ -1035,10 +1036,31 @@ __global__ __launch_bounds__(WG) void k_reset(ExecParamsDev p, ResetRanges r)
 	if (i < r.listWgs) r.listCounts[i] = 0;
 }
 
+// quiet: the block itself and the parts of its +x / +y / +z neighbours that its cells reach into (their first plane, line or
+// voxel: the fields of blockSign) are of one sign, so none of its cells can be non-trivial.  At the grid's far side the
+// samples are clamped, i.e. the block's own.  0: not quiet; else BC_QUIET, with BC_NEGATIVE where that sign is < 0.
+// (k_run_head gives exactly the blocks that are not quiet their slots, k_cell_map exactly those their map words.)
+__device__ __forceinline__ u32 block_quiet_class(const u16* blockSign, u32 bx, u32 by, u32 bz, u32 cnt)
+{
+	u32 signAll = 3u, signAny = 0u;
+#pragma unroll
+	for (u32 k = 0; k < 8; ++k) {
+		u32 f = k;
+		u32 cx = bx + (k & 1u), cy = by + ((k >> 1) & 1u), cz = bz + (k >> 2);
+		if (cx >= cnt) { cx = bx; f &= ~1u; }
+		if (cy >= cnt) { cy = by; f &= ~2u; }
+		if (cz >= cnt) { cz = bz; f &= ~4u; }
+		const u32 sg = ((u32)blockSign[block_coord_id(cx, cy, cz, cnt)] >> (2u * f)) & 3u;
+		signAll &= sg; signAny |= sg;
+	}
+	return (signAll == signAny && signAll != 0u) ? (BC_QUIET | (signAll == 2u ? (u32)BC_NEGATIVE : 0u)) : 0u;
+}
+
 // allocate: the blocks that are not quiet get their level-0 slots here, and their ancestors the slots of the levels above
 // (what k_classify + k_hierarchy do for a run whose classification is a pass of its own).  Not quiet means: the 17^3 samples
 // the block's cells read are not of one sign, so at least one cell is non-trivial - exactly the blocks k_classify finds
-// active.  Their bitmaps are then the business of whoever polygonizes them (k_main: f0_walk<.., SELF>, mat_block).
+// active.  Their bitmaps are then the business of whoever polygonizes them (k_main: read from the cell map, Globals::cellMap, or
+// without it formed in place - f0_walk<.., SELF>, mat_block).
 // clockStart: where workgroup 0 leaves the 100 MHz clock as it starts - the start of the run's device_ms (include/voxels_hip.h);
 // nullptr: the run is timed by events.  A header word of the run's set, so only with r.header == nullptr (no reset in here).
 __global__ __launch_bounds__(WG) void k_run_head(ExecParamsDev p, ResetRanges r, u32 allocate, u32* clockStart)
@@ -1073,21 +1095,7 @@ __global__ __launch_bounds__(WG) void k_run_head(ExecParamsDev p, ResetRanges r,
 		all &= s;
 	}
 	u32 c = (all & 1u) ? (u32)BC_SKIPPED : 0u;
-	// quiet: the block itself and the parts of its +x / +y / +z neighbours that its cells reach into (their first plane,
-	// line or voxel: the fields of blockSign) are of one sign, so none of its cells can be non-trivial.  At the grid's far
-	// side the samples are clamped, i.e. the block's own.
-	u32 signAll = 3u, signAny = 0u;
-#pragma unroll
-	for (u32 k = 0; k < 8; ++k) {
-		u32 f = k;
-		u32 cx = bx + (k & 1u), cy = by + ((k >> 1) & 1u), cz = bz + (k >> 2);
-		if (cx >= L.cnt) { cx = bx; f &= ~1u; }
-		if (cy >= L.cnt) { cy = by; f &= ~2u; }
-		if (cz >= L.cnt) { cz = bz; f &= ~4u; }
-		const u32 sg = ((u32)p.G.blockSign[block_coord_id(cx, cy, cz, L.cnt)] >> (2u * f)) & 3u;
-		signAll &= sg; signAny |= sg;
-	}
-	if (signAll == signAny && signAll != 0u) c |= BC_QUIET | (signAll == 2u ? (u32)BC_NEGATIVE : 0u);
+	c |= block_quiet_class(p.G.blockSign, bx, by, bz, L.cnt);
 	if (inRange) p.G.blockClass[id] = (u8)c;
 	if (allocate) {
 		// Level 0: ballot-compacted slots, one reservation per workgroup.  The ancestors on the levels 1 and 2: which of the box's
@@ -1103,6 +1111,9 @@ __global__ __launch_bounds__(WG) void k_run_head(ExecParamsDev p, ResetRanges r,
 		if (threadIdx.x < 3) below[threadIdx.x] = 0;
 		__syncthreads();
 		const bool active = inRange && !(c & BC_QUIET);
+		// (a run with the cell map: the block's cell count is known - requested here, stored with the slot)
+		u32 cells = 1u;
+		if (p.G.cellCount && active) cells = p.G.cellCount[id];
 		const unsigned long long m = __ballot(active);
 		const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 		if (lane == 0) waveActive[wave] = (u32)__popcll(m);
@@ -1158,7 +1169,13 @@ __global__ __launch_bounds__(WG) void k_run_head(ExecParamsDev p, ResetRanges r,
 			slotOrNone = (int)slot;
 			L.slotCoord[slot] = id;
 			L.skip[slot] = (c & BC_SKIPPED) ? 1 : 0;
-			L.ntCount[slot] = 1; // (not known yet: whoever walks the slot counts its cells; 0 would mean "no geometry")
+			// without the cell map: 1 (not known yet: whoever walks the slot counts its cells; 0 would mean "no geometry").  With
+			// it: the block's cells, 0 for a block the emptiness rule skips - what a walk that counts leaves in this place
+			if (p.G.cellCount) {
+				if (c & BC_SKIPPED) cells = 0u;
+				if (cells > (u32)LARGE_THRESHOLD) atomicAdd(p.G.largeBlocks, 1u); // (the host repeats the run with the upper classes)
+			}
+			L.ntCount[slot] = (u16)cells;
 		}
 		if (threadIdx.x < 32u && 1u < levelsRun && ((below[1] >> threadIdx.x) & 1u)) {
 			const LevelDesc& A = p.levels[1];
@@ -1425,6 +1442,89 @@ __global__ __launch_bounds__(WG) void k_classify(ExecParamsDev p, u32 rowGroup, 
 }
 
 // ------------------------------------------------------------------------------------------------------
+// k_cell_map: the cell map of the rank's level-0 blocks (MirrorState::cellMap / cellCount), written where the grid has changed
+// since the last full single-stream run - never by a polygonization.  The classification of k_classify / k_classify_blocks
+// without the slots: a block its blockSign fields prove quiet gets its count of 0 and nothing else;
+// every other block reads its 17 x 17 rows of 17 samples from the brick mirror (16 bytes of the row's brick + the byte behind
+// them, coordinates clamped to the grid like every fetch - the same rows and the same residency as f0_request) and writes its
+// 256 16-bit cell rows and their population count.
+// ------------------------------------------------------------------------------------------------------
+struct CellMapRange { u32 cnt, yb0, yb1, zb0, zb1; };
+constexpr int CM_CHUNK = 64; // level-0 blocks per workgroup of k_cell_map
+
+// A workgroup takes CM_CHUNK consecutive blocks of the range: a lane of its first wave per block for the blockSign test (most
+// blocks of a terrain are quiet and end there), then a WAVE per block that is not quiet, four at a time (a workgroup per
+// block, quiet ones included, cost 245 us at 1024^3: 16 dependent round trips per workgroup for nothing).
+__global__ __launch_bounds__(WG) void k_cell_map(GridView g, MirrorState ms, CellMapRange r)
+{
+	__shared__ u32 rowMask[WG / 64][292]; // per wave, [z * 17 + y]: sign bits of the samples x = 0..16
+	__shared__ u32 active[CM_CHUNK];      // coordinate ids of the chunk's blocks that are not quiet
+	__shared__ u32 activeCount;
+	const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const int n = g.n;
+	const u32 rowsY = r.yb1 - r.yb0, total = r.cnt * rowsY * (r.zb1 - r.zb0);
+	if (wave == 0) {
+		const u32 it = blockIdx.x * (u32)CM_CHUNK + (u32)lane;
+		bool act = false;
+		u32 id = 0;
+		if (it < total) {
+			const u32 bx = it % r.cnt, by = r.yb0 + (it / r.cnt) % rowsY, bz = r.zb0 + it / (r.cnt * rowsY);
+			id = block_coord_id(bx, by, bz, r.cnt);
+			act = block_quiet_class(ms.blockSign, bx, by, bz, r.cnt) == 0u;
+			if (!act) ms.cellCount[id] = 0;
+		}
+		const unsigned long long m = __ballot(act);
+		if (act) active[__popcll(m & ((1ull << lane) - 1ull))] = id;
+		if (lane == 0) activeCount = (u32)__popcll(m);
+	}
+	__syncthreads();
+	const u32 count = activeCount; // (uniform over the workgroup: so are the barriers below)
+	u32* const rm = rowMask[wave];
+	for (u32 k0 = 0; k0 < count; k0 += (u32)(WG / 64)) {
+		const bool mine = k0 + (u32)wave < count;
+		const u32 id = mine ? (u32)__builtin_amdgcn_readfirstlane((int)active[k0 + (u32)wave]) : 0u;
+		u32 bx, by, bz;
+		block_coords(id, r.cnt, bx, by, bz);
+		if (mine) {
+			// the 289 sample rows (y, z) = 0..16 of the block, 64 at a time: the row's 16 bytes in its brick and the byte behind them
+			// (clamped to the grid: the last sample of the row itself), all requested before the first mask is formed
+			const int x0 = (int)bx * 16, xFar = min(x0 + 16, n - 1);
+			uint4 d[5];
+			i8 f[5];
+#pragma unroll
+			for (int q = 0; q < 5; ++q) {
+				const int row = min(lane + q * 64, 288);
+				const int y = min((int)by * 16 + row % 17, n - 1), z = min((int)bz * 16 + row / 17, n - 1);
+				d[q] = *(const uint4*)(g.bDist + brick_offset(g, x0, y, z));
+				f[q] = g.bDist[brick_offset(g, xFar, y, z)];
+			}
+#pragma unroll
+			for (int q = 0; q < 5; ++q) {
+				const int row = lane + q * 64;
+				if (row < 289) rm[row] = sign_nibble(d[q].x) | (sign_nibble(d[q].y) << 4) | (sign_nibble(d[q].z) << 8) | (sign_nibble(d[q].w) << 12) | ((((u32)(f[q] >> 7)) & 1u) << 16);
+			}
+		}
+		__syncthreads();
+		if (mine) {
+			u32 cells = 0;
+#pragma unroll
+			for (int q = 0; q < 4; ++q) {
+				const int t = lane + q * 64, y = t & 15, z = t >> 4; // cell row (y, z): bits x = 0..15
+				const u32 a = rm[z * 17 + y], b = rm[z * 17 + y + 1], c = rm[(z + 1) * 17 + y], e = rm[(z + 1) * 17 + y + 1];
+				const u32 A = a & b & c & e, O = a | b | c | e;
+				const u32 nt = ((O | (O >> 1)) & ~(A & (A >> 1))) & 0xFFFFu;
+				((u16*)(ms.cellMap + (size_t)id * 128))[t] = (u16)nt;
+				cells += (u32)__popc(nt);
+			}
+#pragma unroll
+			for (int o = 32; o > 0; o >>= 1) cells += (u32)__shfl_xor((int)cells, o, 64);
+			if (lane == 0) ms.cellCount[id] = (u16)cells;
+		}
+		__syncthreads(); // the row masks are free for the next four blocks
+	}
+}
+
+// ------------------------------------------------------------------------------------------------------
 // k_hierarchy: ancestors of active level-0 blocks become active on levels 1..levels-1
 // ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(WG) void k_hierarchy(ExecParamsDev p, u32 levels)
@@ -1516,10 +1616,11 @@ __device__ __forceinline__ u32 vote8_mostly_uniform(const u32 e[8], bool active)
 
 // One block of one level >= 1.  GATED (k_main): the children's caches come from other workgroups of the same launch - waited
 // for right in front of the vote, the only phase that reads them - and the block's own completion is published.
-template <bool GATED, bool PARTIAL = false>
-// selfChild (level 1): the children's consistency bitmaps are not read but formed here, from the children's own samples -
-// the run has no classification pass (k_run_head<allocate>), and the level-0 blocks that form their bitmaps themselves run
-// beside this block, in no order.
+template <bool GATED, bool PARTIAL = false, bool CELLMAP = false>
+// selfChild (level 1): the run has no classification pass (k_run_head<allocate>), and the level-0 blocks that write the
+// bitmaps of their slots run beside this block, in no order: the children's consistency bitmaps are not read by slot.
+// CELLMAP: they are read by child coordinate from the cell map (Globals::cellMap, current before the run starts) and masked
+// by the children's skip flags; otherwise they are formed here, from the children's own samples.
 // boxLo / boxHi (incremental runs inside k_main): only the children inside this box of block coordinates are part of the run and
 // publish; the others' caches are what earlier launches left.
 // PARTIAL (vx_polygonize_from, emitFrom >= 1: no level-0 walk, no meshes below emitFrom): a level-1 block also writes what the
@@ -1593,7 +1694,18 @@ __device__ __forceinline__ void mat_block(const ExecParamsDev& p, u32 level, u32
 	}
 	// ---- child bitmaps (level 1) requested while the rows are classified -----------------------------
 	u32 cb4[4] = { 0, 0, 0, 0 };
-	if (level == 1 && selfChild) {
+	if (level == 1 && selfChild && CELLMAP) {
+		// a child with a slot is not quiet, so its map words are there; absent children and children without a slot read as zero
+		if (tid < 8) st.childSkip[tid] = st.childSlot[tid] >= 0 ? (u32)C.skip[st.childSlot[tid]] : 1u;
+#pragma unroll
+		for (int q = 0; q < 4; ++q) {
+			const int w = tid + q * WG, ci = w >> 7;
+			if (st.childSlot[ci] >= 0) {
+				const u32 cid = block_coord_id(bx * 2 + (u32)(ci & 1), by * 2 + (u32)((ci >> 1) & 1), bz * 2 + (u32)(ci >> 2), C.cnt);
+				cb4[q] = p.G.cellMap[(size_t)cid * 128 + (w & 127)];
+			}
+		}
+	} else if (level == 1 && selfChild) {
 		// The 2 x 2 x 2 children span 33 x 33 sample rows (Y, Z) of 33 samples; a row is two 16-byte pieces of the brick mirror
 		// (x half h = the child column) and the sample behind them.  Sign masks: 16 bits per piece, one byte per far sample,
 		// on top of the vote list (written after the bitmaps are complete).  A piece only some absent child would read is
@@ -1683,7 +1795,10 @@ __device__ __forceinline__ void mat_block(const ExecParamsDev& p, u32 level, u32
 		if (!THROUGH) ((u16*)(L.ntBits + (size_t)slot * 128))[tid] = (u16)nt;
 		if (nt) atomicAdd(&st.ntTotal, (u32)__popc(nt));
 	}
-	if (level == 1 && selfChild) {
+	if (level == 1 && selfChild && CELLMAP) {
+#pragma unroll
+		for (int q = 0; q < 4; ++q) { const int w = tid + q * WG; st.childBits[w >> 7][w & 127] = st.childSkip[w >> 7] ? 0u : cb4[q]; }
+	} else if (level == 1 && selfChild) {
 		const u32* rowW = (const u32*)st.voteList;
 		const u8* farBit = (const u8*)st.voteList + 1089 * 4;
 		const bool lastHalf = (int)(bx * 32) + 16 >= n; // the grid ends behind the first child column: sample 16 = sample 15
@@ -3143,7 +3258,7 @@ struct Backend {
 	int device = 0;
 	bool ok = true;
 	// launch geometry knobs, read from the environment once when the context is created (tuning aids)
-	// Runtime knobs (read once per context).  Eight in all with VX_POOL_SLACK and VX_HOST_TIMING (vx_host.inl); each selects a path
+	// Runtime knobs (read once per context).  Nine in all with VX_POOL_SLACK and VX_HOST_TIMING (vx_host.inl); each selects a path
 	// that production runs reach through their data - dense surfaces, grids beyond 1024^3, blocks with zero samples - so that the
 	// tests can drive those paths on small fixtures (tests/test_gpu_parity.py::test_hip_runtime_knobs_select_equivalent_paths).
 	struct Tuning {
@@ -3154,6 +3269,7 @@ struct Backend {
 		u32 selfHead = 1;    // VX_SELF_HEAD=0: a classification pass (k_classify, k_hierarchy) instead of k_run_head handing out the slots
 		u32 dirtyFused = 1;  // VX_DIRTY_FUSED=0: incremental runs as the chain of launches with work lists
 		u32 syncWait = 0;    // VX_SYNC_WAIT=1: a full run is waited for with hipStreamSynchronize where the default waits for its header (wait_published)
+		u32 cellMap = 1;     // VX_CELLMAP=0: no cell map - the level-0 blocks of a single-stream run form their own bitmaps, its level-1 material blocks their children's
 		// fixed since round 6 (were environment variables while they were being measured; profiles/HISTORY.md has the sweeps)
 		static constexpr u32 classifyRowGroup = 4, regWgsPerCu = 20, f1WgsPerCu = 20, foldBlocks = 65536, upWgsPerCu = 5, mainWgsPerCu = 4, mainBatch = 2, mainUpperNum = 1, mainUpperDen = 4;
 		bool fast0() const { return (fast & 1u) != 0; }
@@ -3187,6 +3303,7 @@ struct Backend {
 		tune.selfHead = env_u32("VX_SELF_HEAD", 1);
 		tune.dirtyFused = env_u32("VX_DIRTY_FUSED", 1);
 		tune.syncWait = env_u32("VX_SYNC_WAIT", 0);
+		tune.cellMap = env_u32("VX_CELLMAP", 1);
 		hipDeviceProp_t prop;
 		if (hipGetDeviceProperties(&prop, device) == hipSuccess) cus = prop.multiProcessorCount;
 		if (!check(hipStreamCreateWithFlags(&ownStream, hipStreamNonBlocking), "hipStreamCreate")) { err = lastError; return false; }
@@ -3235,6 +3352,7 @@ struct Backend {
 		    || !check(hipFuncSetAttribute((const void*)k_transition<false>, hipFuncAttributeMaxDynamicSharedMemorySize, trLds), "hipFuncSetAttribute(k_transition)")
 		    || !check(hipFuncSetAttribute((const void*)k_transition<true>, hipFuncAttributeMaxDynamicSharedMemorySize, trLds), "hipFuncSetAttribute(k_transition, wide)")
 		    || !check(hipFuncSetAttribute((const void*)k_main<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(UP_TAB_LDS + MAIN_STATE_LDS)), "hipFuncSetAttribute(k_main)")
+		    || !check(hipFuncSetAttribute((const void*)k_main<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(UP_TAB_LDS + MAIN_STATE_LDS)), "hipFuncSetAttribute(k_main, cell map)")
 		    || !check(hipFuncSetAttribute((const void*)k_main<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(UP_TAB_LDS + MAIN_STATE_LDS)), "hipFuncSetAttribute(k_main, incremental)")
 		    || !check(hipFuncSetAttribute((const void*)k_main<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(UP_TAB_LDS + MAIN_STATE_LDS)), "hipFuncSetAttribute(k_main, partial)")) {
 			err = lastError;
@@ -3271,6 +3389,18 @@ struct Backend {
 			hipLaunchKernelGGL(k_rebrick, dim3((u32)(groups * yc * zc)), dim3(WG), 0, stream, g, r, ms, box[0], yc, box[2], (const u32*)nullptr);
 		}
 		check(hipGetLastError(), "k_rebrick launch");
+	}
+	// Does a context with a grid of edge n keep the cell map?  Where its full runs can be single-stream ones (single_stream:
+	// the knobs as below, mirrors below 4 GiB).
+	bool wants_cell_map(u32 n) const { return tune.cellMap && tune.upper && tune.fast0() && tune.fast1() && tune.selfHead && !tune.forceWide && n <= 1024u; }
+	// the cell map of the level-0 blocks [yb0, yb1) x [zb0, zb1) (all x) from the brick mirror and the sign summaries
+	void run_cell_map(const GridView& g, const MirrorState& ms, u32 yb0, u32 yb1, u32 zb0, u32 zb1)
+	{
+		const CellMapRange r = { (u32)g.n >> 4, yb0, yb1, zb0, zb1 };
+		const unsigned long long blocks = (unsigned long long)r.cnt * (yb1 - yb0) * (zb1 - zb0);
+		if (!blocks || yb1 <= yb0 || zb1 <= zb0) return;
+		hipLaunchKernelGGL(k_cell_map, dim3((u32)((blocks + CM_CHUNK - 1) / CM_CHUNK)), dim3(WG), 0, stream, g, ms, r);
+		check(hipGetLastError(), "k_cell_map launch");
 	}
 	void make_current() { (void)hipSetDevice(device); }
 	void set_stream(void* s) { stream = s ? (hipStream_t)s : ownStream; }
@@ -3782,7 +3912,9 @@ struct Backend {
 			// (no level-0 queue: the persistent workgroups are the upper queue's)
 			plan.level0 = 0u; plan.upperNum = plan.upperDen = 1u; plan.emitFrom = emitFrom;
 			launch_with_event(k_main<false, true>, dim3(grid), UP_TAB_LDS + MAIN_STATE_LDS, dev(p), plan);
-		} else
+		} else if (withLevel0 && p.G.cellMap)
+			launch_with_event(k_main<false, false, true>, dim3(grid), UP_TAB_LDS + MAIN_STATE_LDS, dev(p), plan);
+		else
 			launch_with_event(k_main<false>, dim3(grid), UP_TAB_LDS + (withLevel0 ? MAIN_STATE_LDS : UP_STATE_LDS), dev(p), plan);
 		check(hipGetLastError(), "k_main launch");
 	}

@@ -73,6 +73,10 @@ struct vx_ctx {
 	void* dBlockSign = nullptr;          // per level-0 block: sign summary of its samples (MirrorState)
 	u32 brickN = 0, brickYb0 = 0, brickZb0 = 0, brickRowsY = 0, brickPlanesZ = 0;
 	bool bricksStale = true;
+	// the cell map (MirrorState::cellMap / cellCount), allocated with the bricks where full runs can be single-stream ones;
+	// stale = a byte of the distance mirror or a sign summary has been written since it was built (ensure_cell_map)
+	void *dCellMap = nullptr, *dCellCount = nullptr;
+	bool cellMapStale = true;
 	void* dListCounts = nullptr;                         // listed blocks per LIST_WG block coordinates, all levels (LevelDesc::listCounts)
 	// Two sets of what a full run needs in its start state - the header's counters, the block -> slot maps of the levels >= 1,
 	// the list counts: a run works on one set, and its last kernel (k_tail) resets the other for the run behind it, which then
@@ -237,6 +241,9 @@ void free_bricks(vx_ctx* c)
 {
 	for (void*& b : c->dBrick) { c->be.free(b); b = nullptr; }
 	c->be.free(c->dBlockSign); c->dBlockSign = nullptr;
+	c->be.free(c->dCellMap); c->dCellMap = nullptr;
+	c->be.free(c->dCellCount); c->dCellCount = nullptr;
+	c->cellMapStale = true;
 	c->brickN = 0;
 	c->bricksStale = true;
 }
@@ -273,6 +280,7 @@ MirrorState mirror_state(const vx_ctx* c)
 	for (u32 L = 0; L < PYRAMID_LEVELS; ++L) ms.pyr[L] = c->pyr[L];
 	for (u32 L = 0; L < XPLANE_LEVELS; ++L) ms.xp[L] = c->xp[L];
 	ms.blockSign = (u16*)c->dBlockSign;
+	ms.cellMap = (u32*)c->dCellMap; ms.cellCount = (u16*)c->dCellCount;
 	ms.yBegin = (int)c->yBegin; ms.yEnd = (int)c->yEnd; ms.zBegin = (int)c->zBegin; ms.zEnd = (int)c->zEnd;
 	return ms;
 }
@@ -294,14 +302,38 @@ bool ensure_bricks(vx_ctx* c)
 		c->dBlockSign = c->be.alloc((size_t)nb * nb * nb * 2);
 		if (!c->dBrick[0] || !c->dBrick[1] || !c->dBrick[2] || !c->dBlockSign) { free_bricks(c); return false; }
 		if (!c->be.fill(c->dBlockSign, 0, (size_t)nb * nb * nb * 2)) { free_bricks(c); return false; } // blocks outside the resident range: unknown
+#if defined(VX_BACKEND_CELL_MAP)
+		if (c->be.wants_cell_map(c->n)) {
+			// by block coordinate of the whole grid, like the sign summaries (a rank fills and reads its own range): 128.5 MB at 1024^3
+			c->dCellMap = c->be.alloc((size_t)nb * nb * nb * 512);
+			c->dCellCount = c->be.alloc((size_t)nb * nb * nb * 2);
+			if (!c->dCellMap || !c->dCellCount) { free_bricks(c); return false; }
+		}
+#endif
 		c->brickN = c->n; c->brickYb0 = yb0; c->brickZb0 = zb0; c->brickRowsY = yb1 - yb0; c->brickPlanesZ = zb1 - zb0;
 	}
 	if (c->bricksStale) {
 		const int box[4] = { (int)yb0, (int)yb1, (int)zb0, (int)zb1 };
 		c->be.run_rebrick(resident_view(c), dr, mr, mirror_state(c), box, nullptr, 0);
 		c->bricksStale = false;
+		c->cellMapStale = true;
 	}
 	return true;
+}
+
+// The cell map brought up to date over the rank's own block range: at the start of a full single-stream run, beside
+// ensure_bricks (and by vx_grid_cell_map).  Nothing to do while no mirror byte has changed since the last time - and nothing
+// is done where the grid changes: incremental runs never read the map and pay no launch for it.
+bool cell_map_pending(const vx_ctx* c) { return c->dCellMap && c->cellMapStale; }
+void ensure_cell_map(vx_ctx* c)
+{
+#if defined(VX_BACKEND_CELL_MAP)
+	if (!cell_map_pending(c) || c->bricksStale) return;
+	c->be.run_cell_map(resident_view(c), mirror_state(c), c->yBegin / 16, c->yEnd / 16, c->zBegin / 16, c->zEnd / 16);
+	c->cellMapStale = false;
+#else
+	(void)c;
+#endif
 }
 
 // the mirrors of the listed blocks (device id list) follow a change of the dense fields; nothing to do while the mirrors
@@ -311,6 +343,7 @@ void rebrick_blocks(vx_ctx* c, const u32* dIds, u32 count)
 	if (!c->be.wants_bricks() || c->bricksStale || !c->dBrick[0] || !count) return;
 	int dr[4], mr[4];
 	resident_ranges(c, dr, mr);
+	c->cellMapStale = true; // (the cells of the listed blocks and of their -x / -y / -z neighbours: the next full run rebuilds the map)
 	c->be.run_rebrick(resident_view(c), dr, mr, mirror_state(c), nullptr, dIds, count);
 }
 
@@ -1175,6 +1208,38 @@ int vx_grid_invalidate(vx_ctx* c)
 	return VX_OK;
 }
 
+int vx_grid_cell_map(vx_ctx* c, uint32_t bx, uint32_t by, uint32_t bz, uint32_t out[128], uint32_t* count)
+{
+	VX_ENTER(c);
+	if (!c || !c->n || !c->dDist) return fail(c, VX_ERR_INVALID, "vx_grid_cell_map: no grid resident");
+	if (!out && !count) return fail(c, VX_ERR_INVALID, "vx_grid_cell_map: null arguments");
+#if defined(VX_BACKEND_CELL_MAP)
+	const u32 nb = c->n / 16;
+	if (!c->be.wants_cell_map(c->n)) return fail(c, VX_ERR_INVALID, "vx_grid_cell_map: this context keeps no cell map (VX_CELLMAP=0, a knob that rules out single-stream runs, or a grid beyond 1024^3)");
+	if (bx >= nb || by < c->yBegin / 16 || by >= c->yEnd / 16 || bz < c->zBegin / 16 || bz >= c->zEnd / 16) return fail(c, VX_ERR_INVALID, "vx_grid_cell_map: block outside the context's range");
+	if (!ensure_level_tables(c)) return fail(c, VX_ERR_DEVICE, "vx_grid_cell_map: level table allocation failed: " + c->be.error());
+	// (a grid that changed as a whole has its mirrors rebuilt here, not by the next run: what that run would have done beside
+	// the rebuild - forget what the run before handed to the general passes - is done here too)
+	const bool stale = c->bricksStale;
+	if (!ensure_bricks(c)) return fail(c, VX_ERR_DEVICE, "vx_grid_cell_map: mirror allocation failed: " + c->be.error());
+	if (stale) c->be.slowHint[0] = c->be.slowHint[1] = ~0u;
+	ensure_cell_map(c);
+	const u32 id = block_coord_id(bx, by, bz, nb);
+	u16 cells = 0;
+	if (!c->be.d2h(&cells, (const u16*)c->dCellCount + id, 2)) return fail(c, VX_ERR_DEVICE, "vx_grid_cell_map: copy failed: " + c->be.error());
+	if (count) *count = cells;
+	if (out) {
+		// (a block without cells is quiet or has an all-zero entry: the words of a quiet block are not read)
+		if (!cells) memset(out, 0, 512);
+		else if (!c->be.d2h(out, (const u32*)c->dCellMap + (size_t)id * 128, 512)) return fail(c, VX_ERR_DEVICE, "vx_grid_cell_map: copy failed: " + c->be.error());
+	}
+	return VX_OK;
+#else
+	(void)bx; (void)by; (void)bz;
+	return fail(c, VX_ERR_INVALID, "vx_grid_cell_map: not supported by this backend (it keeps no mirrors)");
+#endif
+}
+
 int vx_ctx_forget_hints(vx_ctx* c)
 {
 	VX_ENTER(c);
@@ -1269,6 +1334,7 @@ void refresh_halo_layers(vx_ctx* c)
 	const bool alongY = c->slabAxis == 2;
 	const int yb0 = (int)c->brickYb0, yb1 = yb0 + (int)c->brickRowsY, zb0 = (int)c->brickZb0, zb1 = zb0 + (int)c->brickPlanesZ;
 	const int own0 = (int)(alongY ? c->yBegin : c->zBegin) / 16, own1 = (int)(alongY ? c->yEnd : c->zEnd) / 16;
+	c->cellMapStale = true;
 	auto layers = [&](int l0, int l1) {
 		if (l1 <= l0) return;
 		const int box[4] = { alongY ? l0 : yb0, alongY ? l1 : yb1, alongY ? zb0 : l0, alongY ? zb1 : l1 };
@@ -1331,6 +1397,7 @@ int vx_halo_exchange(vx_ctx* c)
 	                                    pl.hasHi ? c->haloBuf[3] : nullptr, pl.hasHi ? halo_move_bytes(pl.recvHi) : 0);
 	if (!ok) return fail(c, VX_ERR_DEVICE, "vx_halo_exchange: " + c->be.error());
 	c->be.run_halo_moves(pl.hasLo ? &pl.recvLo : nullptr, pl.hasHi ? &pl.recvHi : nullptr, halo_view(c), mirror_state(c), alongY);
+	c->cellMapStale = true; // (the unpack writes the received rows into the bricks: the cells of the last owned block layer read them)
 	refresh_halo_layers(c);
 	c->haveSurface = false;
 	return VX_OK;
@@ -1363,6 +1430,7 @@ int vx_halo_exchange_group(vx_ctx* const* ctxs, int count)
 		VX_ENTER(c);
 		if (!c->be.sync_ok()) return fail(c, VX_ERR_DEVICE, "vx_halo_exchange_group: copy failed: " + c->be.error());
 		c->be.run_halo_moves(plans[(size_t)i].hasLo ? &plans[(size_t)i].recvLo : nullptr, plans[(size_t)i].hasHi ? &plans[(size_t)i].recvHi : nullptr, halo_view(c), mirror_state(c), c->slabAxis == 2);
+		c->cellMapStale = true;
 		refresh_halo_layers(c);
 		c->haveSurface = false;
 	}
@@ -1496,7 +1564,7 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 	// (a run behind a run: not waited for - every other entry point has settled, so the grid, the mirrors and the tables are
 	// what the run in flight works on; a changed grid settles all the same, before anything is rebuilt or freed)
 	VX_ENTER_RUN(c);
-	if (c && (c->bricksStale || !c->vertCap)) settle_run(c);
+	if (c && (c->bricksStale || !c->vertCap || cell_map_pending(c))) settle_run(c);
 	if (!c || !c->n || !c->dDist) return fail(c, VX_ERR_INVALID, "vx_polygonize: no grid resident (call vx_grid_upload / vx_grid_attach first)");
 	if (!ensure_level_tables(c)) return fail(c, VX_ERR_DEVICE, "vx_polygonize: level table allocation failed: " + c->be.error());
 	++c->meshEpoch;
@@ -1549,6 +1617,20 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 		// a partial run (first_meshed_level > 0) exists on the single-stream path only; anything else meshes every level and says so
 		emitFrom = (first_meshed_level && c->be.partial_applies(p, levels)) ? std::min<u32>(first_meshed_level, levels) : 0u;
 		c->be.emitFrom = emitFrom;
+#if defined(VX_BACKEND_CELL_MAP)
+		// a full single-stream run that meshes every level reads the cell map: brought up to date first, as part of the mirror
+		// build it belongs to (added to mirror_ms; only a run on a changed grid pays it).  The one place where a run does this:
+		// whether it is a single-stream run is known here, with the attempt's parameters.  Every other run is not shown the map.
+		if (c->dCellMap && !emitFrom && c->be.single_stream(p, levels)) {
+			if (cell_map_pending(c)) {
+				settle_run(c);
+				c->be.begin_timing();
+				ensure_cell_map(c);
+				mirrorMs += c->be.end_timing_ms();
+			}
+			p.G.cellMap = (const u32*)c->dCellMap; p.G.cellCount = (const u16*)c->dCellCount;
+		}
+#endif
 		// device time: two clock words of the header on the single-stream path; the event pair on the chain of launches, with
 		// stage timing and under VX_HOST_TIMING (a recorded event is a packet of its own in the stream: ~8 us before the next kernel)
 		const bool byClock = !hostTiming && RunClock::applies(c->be, p, levels);

@@ -1,6 +1,9 @@
 // vx_main.inl — k_main: everything a full run does between k_run_head (slots) and k_tail (lists) as ONE launch (gfx950).
-// There is no classification pass in front of it: level-0 blocks form their own bitmaps (f0_walk<.., SELF>), level-1
-// material blocks their children's (mat_block, selfChild).  Included by vx_hip.hip
+// There is no classification pass in front of it.  Level-0 blocks and level-1 material blocks read the bitmaps they need by
+// block coordinate from the cell map (MAP: Globals::cellMap, a mirror of the grid that is current before the run starts -
+// MirrorState, ensure_cell_map); k_run_head has taken the blocks' cell counts from it.  Without the map (VX_CELLMAP=0) level-0
+// blocks form their own bitmaps (f0_walk<.., SELF>) and level-1 material blocks their children's (mat_block, selfChild).
+// Included by vx_hip.hip
 // behind the passes whose per-block bodies it calls: f0_walk (table-driven regular cells of level-0 blocks, vx_fast0.inl),
 // mat_block (the material vote of one block of a level >= 1, vx_hip.hip), f1_block (the table-driven regular cells of one
 // block of a level 1..3, vx_fast1.inl), tr_block (the transition cells of one block, vx_hip.hip, with the table-driven body
@@ -41,7 +44,8 @@ struct MainPlan {
 	u32 levels;     // levels of the run: material items for 1 .. levels - 1
 	u32 fastEnd;    // regular items for the levels 1 .. fastEnd - 1 (the levels with a lattice copy)
 	u32 level0;     // 1: the level-0 queue is part of the launch (its LDS then holds a Fast0State), and no classification pass ran
-	                // (k_run_head<allocate>): level-0 blocks and level-1 material blocks form the bitmaps they need
+	                // (k_run_head<allocate>): level-0 blocks and level-1 material blocks read the bitmaps they need from the cell
+	                // map (k_main<false, false, true>) or form them (k_main<false>)
 	u32 batch;      // level-0 slots per dequeue (one head for the chip: a head per XCD over spatial granules - round 6,
 	                // profiles/r06_xcd_heads.txt - fetched 9 % fewer lines and was no faster)
 	u32 upperNum, upperDen; // workgroups with blockIdx % upperDen < upperNum prefer the upper queue
@@ -63,7 +67,8 @@ struct MainPlan {
 // PARTIAL: the levels below plan.emitFrom are somebody else's to mesh (the helper devices of a multi-device Execute): their
 // material blocks run as always - the caches a later Modification continues from - and the level-1 material blocks also
 // write the bitmaps of their level-0 children, which no level-0 walk forms in such a run.
-template <bool DIRTY, bool PARTIAL = false>
+// MAP (full runs with the level-0 queue only): the cell map is current - nobody forms a bitmap.
+template <bool DIRTY, bool PARTIAL = false, bool MAP = false>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_main(ExecParamsDev pArg, MainPlan plan)
 {
 #define MAIN_PARAMS() (void)pArg; const ExecParamsDev& p = kernarg_params() // (vx_hip.hip: read afresh, per item)
@@ -124,7 +129,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 			const u32 first = r0_uniform(sh.nextItem[turn]);
 			if (first >= total0) { level0Left = false; continue; }
 			if (tabKind != 1u) { FT = f0_stage_tables(tab, p.tables, (u32)tid); tabKind = 1u; } // (visible after the walk's first barrier)
-			f0_walk<REG_CAP_SMALL, false, !DIRTY>(FT, *(Fast0State<REG_CAP_SMALL>*)state, wgStats, sh.zeroFlag0, parity0, total0, 0u, first, 1u, min(first + plan.batch, total0), tid);
+			f0_walk<REG_CAP_SMALL, false, !DIRTY && !MAP, MAP>(FT, *(Fast0State<REG_CAP_SMALL>*)state, wgStats, sh.zeroFlag0, parity0, total0, 0u, first, 1u, min(first + plan.batch, total0), tid);
 			continue;
 		}
 		// ---- one item of the upper queue (a few thousand items per run) ---------------------------------------------------
@@ -145,6 +150,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 				if (level >= plan.fastEnd && tid0 == 0) p.G.slowItems[1][atomicAdd(&p.G.slowCount[1], 1u)] = (level << 24) | slot;
 			} else if (PARTIAL)
 				mat_block<true, true>(p, level, slot, *(MatLds*)state, tid, true, nullptr, nullptr, plan.emitFrom);
+			else if (MAP)
+				mat_block<true, false, true>(p, level, slot, *(MatLds*)state, tid, true);
 			else
 				mat_block<true>(p, level, slot, *(MatLds*)state, tid, plan.level0 != 0u);
 			continue;
