@@ -638,6 +638,74 @@ int vx_lod_select(vx_ctx* ctx, const vx_lod_params* params, uint32_t draw_capaci
  * first_meshed_level > 0), a NaN camera, plane or range, n_planes > 6, null params or counts, and null arrays with a
  * non-zero capacity. */
 
+/* ---- scattering: seeded instance points on a level's meshes ------------------------------------------------------------------
+ * Places points (grass, rocks, trees, decals, spawn points) on the surface, next to the meshes, as an instance buffer a
+ * renderer can draw from; vx_scatter_range addresses each block's points by vx_lod_draw.entry.  No reference counterpart:
+ * doc_source/Rendering.md leaves everything after the vertex buffers to the client.
+ *   scope      the REGULAR triangles of one level, as the last run on this context left them (the blocks of
+ *              vx_device_block_table(level)): the scope and staleness of the ray casts.  Transition meshes are not scattered
+ *              on.  Mesh space: Y-up, voxels.
+ *   hash       mix(x): x ^= x>>16; x *= 0x7feb352d; x ^= x>>15; x *= 0x846ca68b; x ^= x>>16, uint32 arithmetic that wraps.
+ *              U(h) = (float)(h >> 8) * 2^-24 (exact).  Per block hb = mix(seed ^ mix(coord_id + 0x9E3779B9 * (level + 1))); per
+ *              triangle ordinal t, ht = mix(hb + t * 0x85EBCA6B); draw j of a triangle d(j) = mix(ht ^ (j * 0xC2B2AE35)), so
+ *              d(0) = mix(ht).  The key is (seed, level, coord_id, t, j), all spatial - not block_id, a running counter: the
+ *              same surface gives the same points whether it came from a full run or from a chain of incremental runs.
+ *   visited    an entry is visited when its table box meets the filter box: min_corner[a] <= box_max[a] && max_corner[a] >=
+ *              box_min[a] on every axis.  Other entries get count = 0 and none of their triangles are looked at.
+ *   candidates of triangle t (vertices v0, v1, v2 in index order), in float32, one rounding per written operation, no
+ *              contraction: e1 = v1 - v0, e2 = v2 - v0; c = (e1.y*e2.z - e1.z*e2.y, e1.z*e2.x - e1.x*e2.z, e1.x*e2.y - e1.y*e2.x);
+ *              l2 = (c.x*c.x + c.y*c.y) + c.z*c.z; m = min((0.5f * sqrtf(l2)) * density, 65535.0f); base = (uint32)m;
+ *              frac = m - (float)base; count = base + (U(d(0)) < frac ? 1 : 0).  No candidates when l2 is zero or not finite,
+ *              or when the texture mask rejects the triangle.
+ *   candidate  k in 0..count-1: r1 = U(d(3k+1)), r2 = U(d(3k+2)); if r1 + r2 > 1.0f then r1 = 1.0f - r1, r2 = 1.0f - r2;
+ *              rand = U(d(3k+3)).  Per axis pos = v0 + (e1*r1 + e2*r2) and g = n0 + ((n1 - n0)*r1 + (n2 - n0)*r2);
+ *              gl = sqrtf((g.x*g.x + g.y*g.y) + g.z*g.z); nrm = g / gl when gl > 0, else zeros.  A candidate is kept when it
+ *              passes the up and box comparisons given in the struct.  Filters never change a draw: the filtered output is
+ *              the unfiltered output with the predicate applied.
+ *   normals    vertex normals are the normalised grid gradient, so they point from solid to air: a floor has nrm.y > 0, a
+ *              ceiling nrm.y < 0.
+ *   order      points by entry, then triangle ordinal, then k; no atomics decide order.  ranges[e] = {points before entry e,
+ *              kept points of entry e} for every entry of the table.  Arrays are filled up to `capacity`; counts is always
+ *              complete.  If points > UINT32_MAX, no point or range is written.
+ *   stale      tables, offsets and meshes are those of the last run (vx_device_block_table).
+ * The per-entry scratch (32 bytes per entry of the largest table) is kept with the context and only ever grown; calls on one
+ * context must be ordered on one stream, as for the LOD selection. */
+#define VX_SCATTER_MAX_DENSITY 64.0f
+#define VX_SCATTER_MAX_PER_TRIANGLE 65535u
+typedef struct vx_scatter_params {      /* 80 bytes */
+	uint32_t seed;
+	float    density;          /* expected points per unit of mesh area (voxel^2): finite, 0 < density <= VX_SCATTER_MAX_DENSITY */
+	float    min_up, max_up;   /* keep points with min_up <= nrm.y <= max_up (mesh space, Y up); -1 / +1 = any slope */
+	float    box_min[3], box_max[3]; /* keep points with box_min <= pos <= box_max per axis, mesh space; -INF / +INF allowed */
+	uint32_t texture_slot;     /* 0..7: which byte of vx_vertex.tex the mask reads */
+	uint32_t texture_mask[8];  /* 256 bits; a triangle takes part when bit tex[texture_slot] of its FIRST vertex is set; all ones = any */
+	uint32_t reserved;         /* 0 */
+} vx_scatter_params;
+typedef struct vx_scatter_point {       /* 48 bytes */
+	float pos[3];  float rand;          /* rand in [0,1): for the application's scale / rotation / variant */
+	float nrm[3];  uint32_t entry;      /* interpolated vertex normal, unit; entry of vx_device_block_table(level) */
+	uint32_t block_id, tri, tex[2];     /* BlockPolygons::GetId; triangle ordinal; the first vertex's 8 tex bytes as TI[0], TI[1] */
+} vx_scatter_point;
+typedef struct vx_scatter_range { uint32_t first, count; } vx_scatter_range;   /* per table entry */
+typedef struct vx_scatter_counts {      /* 32 bytes */
+	uint64_t points;            /* what unlimited capacity would hold */
+	uint64_t candidates;        /* candidate points evaluated, before the per-point filters */
+	uint32_t triangles;         /* triangles of visited entries that pass the texture mask */
+	uint32_t entries, visited_entries, reserved;
+} vx_scatter_counts;
+/* Device arrays (16-byte aligned; d_ranges: 8), enqueued on the context's stream (vx_set_stream), returns without waiting:
+ * three launches, no copy, no synchronisation, and no allocation once the per-entry scratch exists. */
+int vx_scatter_device(vx_ctx*, uint32_t level, const vx_scatter_params* params /* host */, uint32_t capacity,
+                      vx_scatter_point* d_points, vx_scatter_range* d_ranges /* may be NULL */, vx_scatter_counts* d_counts);
+/* Host arrays, synchronous.  VX_ERR_OVERFLOW when points > capacity, after writing the counts, the ranges and the first
+ * `capacity` points (as vx_lod_select does). */
+int vx_scatter(vx_ctx*, uint32_t level, const vx_scatter_params* params, uint32_t capacity,
+               vx_scatter_point* points, vx_scatter_range* ranges /* may be NULL */, vx_scatter_counts* counts);
+/* Both: VX_ERR_INVALID, before anything is launched, for a context without a surface, a level at or beyond what the last run
+ * produced, null params or counts, a null point array with a non-zero capacity, a density that is not finite or outside
+ * (0, VX_SCATTER_MAX_DENSITY], a NaN in any float field, min_up > max_up, box_min > box_max on an axis, texture_slot > 7,
+ * reserved != 0, and (device form) misaligned arrays.  A level with an empty table is VX_OK with zero counts (written). */
+
 /* stats[0..3] = BlocksCalculated, TrivialCells, NonTrivialCells, DegenerateTrianglesRemoved; stats[4..19] =
  * PerCaseCellsCount (include/Polygonizer.h:110-132) */
 int vx_stats(vx_ctx* ctx, uint32_t stats[20]);

@@ -84,6 +84,36 @@ def lod_params(camera, ranges=None, planes=None):
     return prm
 
 
+# vx_scatter_* (include/voxels_hip.h, scattering)
+SCATTER_PARAMS_DTYPE = np.dtype([("seed", "<u4"), ("density", "<f4"), ("min_up", "<f4"), ("max_up", "<f4"), ("box_min", "<f4", 3),
+                                 ("box_max", "<f4", 3), ("texture_slot", "<u4"), ("texture_mask", "<u4", 8), ("reserved", "<u4")])
+SCATTER_POINT_DTYPE = np.dtype([("pos", "<f4", 3), ("rand", "<f4"), ("nrm", "<f4", 3), ("entry", "<u4"), ("block_id", "<u4"),
+                                ("tri", "<u4"), ("tex", "<u4", 2)])
+SCATTER_RANGE_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4")])
+SCATTER_COUNTS_DTYPE = np.dtype([("points", "<u8"), ("candidates", "<u8"), ("triangles", "<u4"), ("entries", "<u4"),
+                                 ("visited_entries", "<u4"), ("reserved", "<u4")])
+assert SCATTER_PARAMS_DTYPE.itemsize == 80 and SCATTER_POINT_DTYPE.itemsize == 48
+assert SCATTER_RANGE_DTYPE.itemsize == 8 and SCATTER_COUNTS_DTYPE.itemsize == 32
+SCATTER_MAX_DENSITY = 64.0
+SCATTER_MAX_PER_TRIANGLE = 65535
+
+
+def scatter_params(seed=0, density=1.0, min_up=-1.0, max_up=1.0, box_min=None, box_max=None, texture_slot=0, texture_values=None):
+    """one SCATTER_PARAMS_DTYPE record; the defaults mean "no filter": any slope, an infinite box, every texture value.
+    texture_values: the values of vertex tex byte `texture_slot` (of a triangle's first vertex) that take part, None = all"""
+    prm = np.zeros(1, SCATTER_PARAMS_DTYPE)
+    prm["seed"], prm["density"], prm["min_up"], prm["max_up"] = seed, density, min_up, max_up
+    prm["box_min"] = -np.inf if box_min is None else box_min
+    prm["box_max"] = np.inf if box_max is None else box_max
+    prm["texture_slot"] = texture_slot
+    if texture_values is None:
+        prm["texture_mask"] = 0xFFFFFFFF
+    else:
+        for v in texture_values:
+            prm["texture_mask"][0, int(v) >> 5] |= np.uint32(1 << (int(v) & 31))
+    return prm
+
+
 class VoxelsHipError(RuntimeError):
     pass
 
@@ -244,6 +274,11 @@ class HipLibrary:
         if self.has_lod:
             lib.vx_lod_select_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
             lib.vx_lod_select.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
+        # scattering: HIP builds only, likewise
+        self.has_scatter = hasattr(lib, "vx_scatter")
+        if self.has_scatter:
+            lib.vx_scatter_device.argtypes = [vp, u32, vp, u32, vp, vp, vp]
+            lib.vx_scatter.argtypes = [vp, u32, vp, u32, vp, vp, vp]
         self.lib = lib
         self.path = path
         self.backend = lib.vx_backend().decode()
@@ -796,6 +831,45 @@ class Polygonizer:
         self._check(self._lod_lib().vx_lod_select_device(self._h, _ptr(prm), int(draw_capacity), int(transition_capacity),
                                                          C.c_void_p(d_draws), C.c_void_p(d_regular), C.c_void_p(d_transition),
                                                          C.c_void_p(d_counts)), "vx_lod_select_device")
+
+    def _scatter_lib(self):
+        if not self._L.has_scatter:
+            raise VoxelsHipError("%s has no scattering (vx_scatter*)" % self._L.path)
+        return self._L.lib
+
+    def scatter_raw(self, level, params, capacity):
+        """one vx_scatter call: (return code, points SCATTER_POINT_DTYPE[capacity], ranges SCATTER_RANGE_DTYPE, counts record)"""
+        lib = self._scatter_lib()
+        prm = np.ascontiguousarray(params, SCATTER_PARAMS_DTYPE)
+        points, counts = np.zeros(int(capacity), SCATTER_POINT_DTYPE), np.zeros(1, SCATTER_COUNTS_DTYPE)
+        ranges = np.zeros(self.device_block_table(level)[1], SCATTER_RANGE_DTYPE)
+        rc = lib.vx_scatter(self._h, int(level), _ptr(prm), int(capacity), _ptr(points) if capacity else None, _ptr(ranges), _ptr(counts))
+        return rc, points, ranges, counts[0]
+
+    def scatter(self, level, params, capacity=None):
+        """vx_scatter: (points SCATTER_POINT_DTYPE, ranges SCATTER_RANGE_DTYPE per table entry, counts dict) for a
+        SCATTER_PARAMS_DTYPE record (scatter_params()).  capacity None: two calls, the counts first, then the fill; with a
+        capacity, at most that many points come back (counts["points"] says how many there are)."""
+        cap = capacity
+        if cap is None:
+            rc, _, _, counts = self.scatter_raw(level, params, 0)
+            if rc != -3:
+                self._check(rc, "vx_scatter")
+            if int(counts["points"]) > 0xFFFFFFFF:
+                raise VoxelsHipError("vx_scatter: %d points do not fit a 32-bit capacity" % int(counts["points"]))
+            cap = int(counts["points"])
+        rc, points, ranges, counts = self.scatter_raw(level, params, cap)
+        if rc != -3 or capacity is None:
+            self._check(rc, "vx_scatter")
+        c = {k: int(counts[k]) for k in SCATTER_COUNTS_DTYPE.names}
+        return points[:min(c["points"], cap)], ranges, c
+
+    def scatter_device(self, level, params, capacity, d_points, d_ranges, d_counts):
+        """vx_scatter_device: params = a SCATTER_PARAMS_DTYPE record (scatter_params()), arrays at device addresses (ints, 16-byte
+        aligned, d_ranges 8 or None); queued on the context's stream (set_stream), returns without waiting."""
+        prm = np.ascontiguousarray(params, SCATTER_PARAMS_DTYPE)
+        self._check(self._scatter_lib().vx_scatter_device(self._h, int(level), _ptr(prm), int(capacity), C.c_void_p(d_points),
+                                                          C.c_void_p(d_ranges), C.c_void_p(d_counts)), "vx_scatter_device")
 
     def stats(self):
         out = np.zeros(20, np.uint32)

@@ -20,7 +20,7 @@ def _newer(target, sources):
 def build_hip(force=False, verbose=True):
     """hipcc --offload-arch=gfx950 ... -o voxels_amd/csrc/libvoxels_hip.so (cross-compiles without a GPU)."""
     out = os.path.join(CSRC, "libvoxels_hip.so")
-    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_lod.inl", "tv_lod.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
+    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_lod.inl", "tv_lod.h", "vx_scatter.inl", "tv_scatter.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
     srcs.append(os.path.join(ROOT, "include", "voxels_hip.h"))
     if not force and not _newer(out, srcs):
         return out
@@ -39,7 +39,8 @@ def build_hip(force=False, verbose=True):
     missing = [k for k in ("k_regular0", "k_regular", "k_transition", "k_classify", "k_material", "k_main", "k_tail", "k_run_head", "k_cell_map", "k_dirty_head", "k_dirty_tail",
                            "k_spherecast", "k_closest_point", "k_brush_apply",
                            "k_isl_local", "k_isl_merge", "k_isl_flatten", "k_isl_scan", "k_isl_roots", "k_isl_stats", "k_isl_mark", "k_isl_compact", "k_isl_remove",
-                           "k_smooth_eval", "k_smooth_commit", "k_smooth_results")
+                           "k_smooth_eval", "k_smooth_commit", "k_smooth_results",
+                           "k_scatter_count", "k_scatter_scan", "k_scatter_write")
                if not any(k in name and "ScratchSize" in v for name, v in table.items())]
     if missing:
         os.remove(out)
@@ -113,7 +114,7 @@ def kernel_resources(remarks):
 def build_hip_casedump(force=False):
     """Test build of the HIP library that also records the case codes it looks up (tests/test_case_codes.py)."""
     out = os.path.join(CSRC, "libvoxels_hip_casedump.so")
-    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_lod.inl", "tv_lod.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
+    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_lod.inl", "tv_lod.h", "vx_scatter.inl", "tv_scatter.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
     if not force and not _newer(out, srcs):
         return out
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -125,7 +126,7 @@ def build_hip_conservative(force=False):
     """Test build of the HIP library whose in-kernel dependency flags use release / acquire fences instead of write-through
     stores and loads (-DVX_CONSERVATIVE_SYNC, vx_hip.hip): tests/test_gpu_parity.py compares it with the product library."""
     out = os.path.join(CSRC, "libvoxels_hip_conservative.so")
-    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_lod.inl", "tv_lod.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
+    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_lod.inl", "tv_lod.h", "vx_scatter.inl", "tv_scatter.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
     if not force and not _newer(out, srcs):
         return out
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -254,6 +255,19 @@ def build_smooth_host(force=False):
         return out
     subprocess.check_call(["g++", "-std=c++14", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-o", out,
                            os.path.join(d, "smooth_host.cpp")], cwd=d)
+    return out
+
+
+def build_scatter_host(force=False):
+    """Host side of the tests of vx_scatter: the arithmetic of csrc/tv_scatter.h in a plain loop over a level's table and meshes, the
+    same float32 operations as the kernels (-ffp-contract=off) - tests only (tests/test_scatter.py, tests/test_abi_scatter.py)."""
+    d = os.path.join(ROOT, "tests", "scatter")
+    out = os.path.join(d, "libvoxels_scatter_host.so")
+    srcs = [os.path.join(d, "scatter_host.cpp"), os.path.join(CSRC, "tv_scatter.h"), os.path.join(ROOT, "include", "voxels_hip.h")]
+    if not force and not _newer(out, srcs):
+        return out
+    subprocess.check_call(["g++", "-std=c++14", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-o", out,
+                           os.path.join(d, "scatter_host.cpp")], cwd=d)
     return out
 
 

@@ -4224,3 +4224,4 @@ struct Backend {
 #include "vx_ray.inl"
 #include "vx_shape.inl"
 #include "vx_lod.inl"
+#include "vx_scatter.inl"

@@ -164,6 +164,9 @@ struct vx_ctx {
 	// smoothing (vx_smooth.inl): its device buffers
 	void* smoothState = nullptr;
 	void (*smoothFree)(vx_ctx*) = nullptr;
+	// scattering (vx_scatter.inl): its device buffers
+	void* scatterState = nullptr;
+	void (*scatterFree)(vx_ctx*) = nullptr;
 };
 
 // What only a backend with a device clock and a header the host can wait on offers (VX_BACKEND_HEADER_WAIT, defined by the
@@ -852,6 +855,7 @@ void vx_ctx_destroy(vx_ctx* c)
 	if (c->brushFree) c->brushFree(c);
 	if (c->islandFree) c->islandFree(c);
 	if (c->smoothFree) c->smoothFree(c);
+	if (c->scatterFree) c->scatterFree(c);
 	c->be.shutdown();
 	delete c;
 }
