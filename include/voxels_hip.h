@@ -358,6 +358,77 @@ typedef struct vx_smooth_result {   /* 32 bytes */
 int vx_grid_smooth(vx_ctx* ctx, const vx_smooth* ops, uint32_t count, vx_smooth_result* results /* may be NULL */,
                    float union_min[3], float union_max[3] /* may be NULL */, uint64_t* changed_voxels /* may be NULL */);
 
+/* ---- walk fields (HIP library only) -----------------------------------------------------------------------------------
+ * vx_grid_walk_field answers "where can my agents still walk, and which way?" on the resident grid: for every voxel of a box
+ * the cost of the cheapest walk to the nearest of a set of goals, and - derived from it - the move to take: the flow field a
+ * crowd reads with one lookup per agent.  The reference has nothing like it.  All arithmetic is in integers and the result is
+ * the unique least solution of the recurrence below: nothing in it depends on scheduling (`sweeps` excepted).
+ * Internal axes with Z up, as vx_island_query; d is the int8 distance sample as stored.
+ *   Solid / air  solid(x, y, z): 0 <= z < n and d < 0.  air(x, y, z): z >= n, or 0 <= z < n and d >= 0.  Below the grid
+ *              (z < 0) is neither.
+ *   Region     a box of voxels [lo, hi), lo < hi <= n per axis, not necessarily aligned to blocks; whole_grid != 0 means the
+ *              whole grid.  Its volume V = ex * ey * ez must be <= 2^28; larger areas are queried box by box.  That bounds the
+ *              field at 1 GiB and the rest of the working memory (below) at 32 MiB for a block-aligned box, about 0.5 GiB for a
+ *              box one voxel thick (every 16^3 block it touches counts whole).
+ *   Standable  a region voxel c = (x, y, z) with z >= 1, solid(x, y, z - 1) and air(x, y, z + k) for k = 0 .. clearance - 1.
+ *              The column is read from the GRID, also below lo.z and above hi.z.  Materials, blends and BF_Empty play no part.
+ *   Moves      c -> c' where c' is standable and inside the region, dz = c'.z - c.z lies in [-step_down, +step_up], and the
+ *              horizontal offset is one of the codes 0..7, in this order: (+1,0) (-1,0) (0,+1) (0,-1) (+1,+1) (-1,+1) (+1,-1)
+ *              (-1,-1).  A diagonal move (dx, dy) exists only when cost_diagonal != 0 and BOTH columns (x + dx, y) and
+ *              (x, y + dy) hold at least one standable in-region cell c'' with c''.z - c.z in [-step_down, +step_up]: there is
+ *              no cutting of corners.  A column can hold several targets (a bridge over a cave floor): each is a move of its
+ *              own.  Weight w = (axial ? cost_axial : cost_diagonal) + |dz| * cost_climb.
+ *   Goals      a host array of vx_walk_goal, at most VX_WALK_MAX_GOALS.  A goal is USED when its cell (grid coordinates) is
+ *              standable, inside the region, and cost <= max_cost; every other goal is IGNORED and counted.  Duplicates are
+ *              legal; the least cost wins.
+ *   Field      F(c) = min(least cost of a used goal at c, min over the moves c -> c' of w + F(c')), the least solution: the cost
+ *              of the cheapest walk from c to a goal.  A cell with F(c) > max_cost, a voxel that is not standable, and a cell
+ *              with no walk to a goal all read VX_WALK_UNREACHED; a cell with F == max_cost is reached.  Dropping every
+ *              candidate above max_cost while relaxing is exact: weights are positive, so every cell further along a cheapest
+ *              walk has a smaller F - a walk whose cost is within max_cost never passes through a cell that was dropped.
+ *   Direction  one byte per region voxel: 0xFF where the field is UNREACHED; 0xFE where no move gives w + F(c') == F(c) (a goal
+ *              cell that is its own best); otherwise the move code offset | (dz + 4) << 3 of a move with w + F(c') == F(c) -
+ *              among several, the least code.
+ *   Limits     clearance 1..32; step_up, step_down 0..4; cost_axial 1..65535; cost_diagonal 0..65535 (0 = no diagonals);
+ *              cost_climb 0..65535; max_cost 0..2^30; flags 0.  With these the largest sum ever formed is
+ *              2^30 + 65535 + 4 * 65535 < 2^31: no sum wraps a uint32.
+ * d_field (optional; device memory, V uint32, x fastest inside the region, 16-byte aligned) receives F; without it the library
+ * uses a working volume of its own.  d_dirs (optional; device memory, V bytes, same order) receives the direction bytes.
+ * counts is always written, also with both outputs NULL: standable cells of the region, reached cells, used and ignored goals,
+ * max_distance = the largest reached F (0 when nothing is reached), and sweeps = how many relaxation sweeps the call ran -
+ * the one field that is NOT part of the deterministic result (it depends on the order the hardware served the tiles in).  Sweeps
+ * are launched in batches of 8 and every launch counts, also the idle ones behind the sweep that changed the last cell: the
+ * number is a multiple of the batch (unless the cap of the loop cuts a batch short), not a measure of convergence.
+ * With no used goal the field is all UNREACHED, reached = 0, and the call returns VX_OK.
+ * VX_ERR_INVALID, with nothing launched and nothing written to d_field / d_dirs (counts, when it is not NULL, is zeroed on
+ * entry, so it reads all zero after such a call), for: a null query or null counts, a bad or too
+ * large box, a limit violated, non-zero flags, goal_count > VX_WALK_MAX_GOALS, a null goal array with a count, a misaligned
+ * d_field, a context that does not own a whole grid (vx_grid_upload / vx_grid_upload_packed).  VX_ERR_DEVICE when working memory
+ * cannot be allocated.  The call never changes the grid, the flags or the mirrors.
+ * Working memory, kept with the context and only ever grown: 4 bytes per region voxel (none of that when d_field is given),
+ * 524 bytes per 16^3 block the region touches (one standable bit per voxel, a count and two sweep flags) and 16 bytes per goal.
+ * The call is synchronous and runs on the context's stream (vx_set_stream).  It waits for the device when the standable cells
+ * are counted, once per batch of relaxation sweeps, and at its end. */
+#define VX_WALK_UNREACHED 0xFFFFFFFFu
+#define VX_WALK_MAX_GOALS 65536u
+typedef struct vx_walk_query {      /* 64 bytes */
+    uint32_t lo[3], hi[3];          /* ignored when whole_grid != 0 */
+    uint32_t whole_grid, clearance, step_up, step_down;
+    uint32_t cost_axial, cost_diagonal, cost_climb, max_cost;
+    uint32_t flags /* 0 */, reserved;
+} vx_walk_query;
+typedef struct vx_walk_goal {       /* 16 bytes */
+    uint32_t x, y, z, cost;
+} vx_walk_goal;
+typedef struct vx_walk_counts {     /* 32 bytes */
+    uint64_t standable, reached;
+    uint32_t goals_used, goals_ignored, max_distance;
+    uint32_t sweeps;                /* not part of the deterministic result */
+} vx_walk_counts;
+int vx_grid_walk_field(vx_ctx* ctx, const vx_walk_query* query, const vx_walk_goal* goals /* host */, uint32_t goal_count,
+                       uint32_t* d_field /* device, may be NULL */, uint8_t* d_dirs /* device, may be NULL */,
+                       vx_walk_counts* counts);
+
 /* MaterialMap::GetMaterial resolved on the host (include/MaterialMap.h:19-30): lut[id] = {DiffuseIds0[3],
  * DiffuseIds1[3]}, valid[id] == 0 means GetMaterial returned NULL (texture bytes stay 0). */
 int vx_material_lut(vx_ctx* ctx, const uint8_t* lut /*256*6*/, const uint8_t* valid /*256*/);

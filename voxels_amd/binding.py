@@ -51,6 +51,15 @@ SMOOTH_DTYPE = np.dtype([("lo", "<u4", 3), ("hi", "<u4", 3), ("center", "<f4", 3
 SMOOTH_RESULT_DTYPE = np.dtype([("out_min", "<f4", 3), ("out_max", "<f4", 3), ("changed_voxels", "<u8")])
 assert SMOOTH_DTYPE.itemsize == 48 and SMOOTH_RESULT_DTYPE.itemsize == 32
 assert POINT_QUERY_DTYPE.itemsize == 16 and POINT_HIT_DTYPE.itemsize == 48
+# vx_walk_query / vx_walk_goal / vx_walk_counts (include/voxels_hip.h, "walk fields")
+WALK_UNREACHED, WALK_MAX_GOALS = 0xFFFFFFFF, 65536
+WALK_QUERY_DTYPE = np.dtype([("lo", "<u4", 3), ("hi", "<u4", 3), ("whole_grid", "<u4"), ("clearance", "<u4"), ("step_up", "<u4"),
+                             ("step_down", "<u4"), ("cost_axial", "<u4"), ("cost_diagonal", "<u4"), ("cost_climb", "<u4"),
+                             ("max_cost", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+WALK_GOAL_DTYPE = np.dtype([("x", "<u4"), ("y", "<u4"), ("z", "<u4"), ("cost", "<u4")])
+WALK_COUNTS_DTYPE = np.dtype([("standable", "<u8"), ("reached", "<u8"), ("goals_used", "<u4"), ("goals_ignored", "<u4"),
+                              ("max_distance", "<u4"), ("sweeps", "<u4")])
+assert WALK_QUERY_DTYPE.itemsize == 64 and WALK_GOAL_DTYPE.itemsize == 16 and WALK_COUNTS_DTYPE.itemsize == 32
 SPHERE_STARTED_IN_CONTACT = 1
 # vx_lod_params / vx_lod_draw / vx_draw_indexed / vx_lod_counts (include/voxels_hip.h, LOD selection)
 LOD_PARAMS_DTYPE = np.dtype([("camera", "<f4", 3), ("n_planes", "<u4"), ("planes", "<f4", (6, 4)), ("ranges", "<f4", 16)])
@@ -270,6 +279,11 @@ class HipLibrary:
         if self.has_smooth:
             lib.vx_grid_smooth.argtypes = [vp, vp, u32, vp, vp, vp, vp]
             lib.vx_grid_smooth.restype = C.c_int
+        # walk fields: HIP builds only, likewise
+        self.has_walk_field = hasattr(lib, "vx_grid_walk_field")
+        if self.has_walk_field:
+            lib.vx_grid_walk_field.argtypes = [vp, vp, vp, u32, vp, vp, vp]
+            lib.vx_grid_walk_field.restype = C.c_int
         self.has_lod = hasattr(lib, "vx_lod_select")
         if self.has_lod:
             lib.vx_lod_select_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
@@ -296,6 +310,28 @@ def island_query(box=None, detached_only=False, remove=False, anchor_faces=0x3F,
     q["max_voxels"] = max_voxels
     q["air_value"] = air_value
     return q
+
+
+def walk_query(box=None, clearance=2, step_up=1, step_down=1, cost_axial=10, cost_diagonal=14, cost_climb=0, max_cost=1 << 30):
+    """one WALK_QUERY_DTYPE record; box = (lo, hi) in grid coordinates (internal axes, Z up), None = the whole grid"""
+    q = np.zeros(1, WALK_QUERY_DTYPE)
+    if box is None:
+        q["whole_grid"] = 1
+    else:
+        q["lo"], q["hi"] = np.asarray(box[0], np.uint32), np.asarray(box[1], np.uint32)
+    q["clearance"], q["step_up"], q["step_down"] = clearance, step_up, step_down
+    q["cost_axial"], q["cost_diagonal"], q["cost_climb"], q["max_cost"] = cost_axial, cost_diagonal, cost_climb, max_cost
+    return q
+
+
+def walk_goals(goals):
+    """a WALK_GOAL_DTYPE array from one, or from rows of (x, y, z) or (x, y, z, cost)"""
+    if isinstance(goals, np.ndarray) and goals.dtype == WALK_GOAL_DTYPE:
+        return np.ascontiguousarray(goals).reshape(-1)
+    g = np.zeros(len(goals), WALK_GOAL_DTYPE)
+    for k, row in enumerate(goals):
+        g[k] = tuple(int(v) for v in row) + (0,) * (4 - len(row))
+    return g
 
 
 def smooth_op(box, center=None, radius=0.0, strength=1.0, iterations=1):
@@ -495,6 +531,28 @@ class Polygonizer:
             raise VoxelsHipError("vx_grid_islands failed (-3): %d records listed, room for %d" % (listed, capacity))
         self._check(rc, "vx_grid_islands")
         return recs[:min(listed, int(capacity))], counts[0].copy(), mn, mx
+
+    def walk_field(self, box, goals, clearance=2, step_up=1, step_down=1, cost_axial=10, cost_diagonal=14, cost_climb=0, max_cost=1 << 30,
+                   field=None, dirs=None):
+        """vx_grid_walk_field: the cost of the cheapest walk from every standable voxel of `box` ((lo, hi), None = the whole
+        grid) to the nearest goal (a WALK_GOAL_DTYPE array, or rows of (x, y, z[, cost])) -> the counts WALK_COUNTS_DTYPE record.
+        field: optional torch device tensor of V int32 / uint32 that receives the field (WALK_UNREACHED where there is no walk);
+        dirs: optional torch device tensor of V uint8 that receives the direction bytes."""
+        if not self._L.has_walk_field:
+            raise VoxelsHipError("this library has no vx_grid_walk_field (HIP builds only)")
+        q = walk_query(box, clearance, step_up, step_down, cost_axial, cost_diagonal, cost_climb, max_cost)
+        g = walk_goals(goals)
+        ext = [self.n] * 3 if box is None else [int(h) - int(l) for l, h in zip(box[0], box[1])]
+        fp = dp = None
+        if field is not None:
+            assert field.is_cuda and field.is_contiguous() and field.element_size() == 4 and field.numel() == ext[0] * ext[1] * ext[2]
+            fp = C.c_void_p(field.data_ptr())
+        if dirs is not None:
+            assert dirs.is_cuda and dirs.is_contiguous() and dirs.element_size() == 1 and dirs.numel() == ext[0] * ext[1] * ext[2]
+            dp = C.c_void_p(dirs.data_ptr())
+        counts = np.zeros(1, WALK_COUNTS_DTYPE)
+        self._check(self._lib.vx_grid_walk_field(self._h, _ptr(q), _ptr(g) if g.size else None, g.size, fp, dp, _ptr(counts)), "vx_grid_walk_field")
+        return counts[0].copy()
 
     def compact_pools(self):
         self._check(self._lib.vx_compact_pools(self._h), "vx_compact_pools")

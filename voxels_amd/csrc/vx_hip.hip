@@ -4221,6 +4221,7 @@ struct Backend {
 #include "vx_brush.inl"
 #include "vx_island.inl"
 #include "vx_smooth.inl"
+#include "vx_walk.inl"
 #include "vx_ray.inl"
 #include "vx_shape.inl"
 #include "vx_lod.inl"

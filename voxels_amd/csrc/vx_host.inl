@@ -167,6 +167,9 @@ struct vx_ctx {
 	// scattering (vx_scatter.inl): its device buffers
 	void* scatterState = nullptr;
 	void (*scatterFree)(vx_ctx*) = nullptr;
+	// walk fields (vx_walk.inl): its device buffers
+	void* walkState = nullptr;
+	void (*walkFree)(vx_ctx*) = nullptr;
 };
 
 // What only a backend with a device clock and a header the host can wait on offers (VX_BACKEND_HEADER_WAIT, defined by the
@@ -856,6 +859,7 @@ void vx_ctx_destroy(vx_ctx* c)
 	if (c->islandFree) c->islandFree(c);
 	if (c->smoothFree) c->smoothFree(c);
 	if (c->scatterFree) c->scatterFree(c);
+	if (c->walkFree) c->walkFree(c);
 	c->be.shutdown();
 	delete c;
 }
