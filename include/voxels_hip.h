@@ -787,6 +787,13 @@ int vx_stats(vx_ctx* ctx, uint32_t stats[20]);
  * meshes are the same either way. */
 int vx_transition_path_counts(vx_ctx* ctx, uint32_t out[2]);
 
+/* Material blocks (active blocks of the levels >= 1) of the last full run by how their material cache came about (both 0
+ * behind an incremental run, which counts none): out[0] = voted from the children, out[1] = replayed from the material store - what the last full single-stream run on this grid
+ * left, copied where nothing the votes read has changed since (distances, materials, blends, BF_Empty flags, the context's
+ * range).  VX_MATSTORE=0 (read at context creation) keeps no store: every run votes.  Diagnostics: caches, meshes and
+ * statistics are the same either way. */
+int vx_material_path_counts(vx_ctx* ctx, uint32_t out[2]);
+
 /* The device forms of the exactness-critical arithmetic checked exhaustively on the GPU they run on (the reference does
  * this arithmetic on the host: t = (v1 << 8) / (v1 - v0), src/TransVoxelImpl.cpp:1591; normalizeFixZero, :93-103):
  * results[0] = crossed int8 sample pairs whose t differs from the truncated quotient, results[1] = gradients whose normal

@@ -243,6 +243,10 @@ class HipLibrary:
         lib.vx_host_meshes_reserve.argtypes = [vp, C.c_uint64, C.c_uint64]
         lib.vx_stats.argtypes = [vp, vp]
         lib.vx_transition_path_counts.argtypes = [vp, vp]
+        # (absent from builds of the library made before the material store: VOXELS_HIP_LIBRARY may name one, for A/B measurements)
+        self.has_material_path_counts = hasattr(lib, "vx_material_path_counts")
+        if self.has_material_path_counts:
+            lib.vx_material_path_counts.argtypes = [vp, vp]
         lib.vx_selftest.argtypes = [vp, vp]
         lib.vx_stage_layout.argtypes = [vp, C.POINTER(C.c_int)]
         lib.vx_set_stage_timing.argtypes = [vp, C.c_int]
@@ -938,4 +942,12 @@ class Polygonizer:
         """vx_transition_path_counts: (table_driven, fallback) transition blocks of the last run."""
         out = np.zeros(2, np.uint32)
         self._check(self._lib.vx_transition_path_counts(self._h, _ptr(out)), "vx_transition_path_counts")
+        return int(out[0]), int(out[1])
+
+    def material_path_counts(self):
+        """vx_material_path_counts: (voted, replayed) material blocks of the last full run."""
+        if not self._L.has_material_path_counts:
+            raise VoxelsHipError("this library has no vx_material_path_counts")
+        out = np.zeros(2, np.uint32)
+        self._check(self._lib.vx_material_path_counts(self._h, _ptr(out)), "vx_material_path_counts")
         return int(out[0]), int(out[1])

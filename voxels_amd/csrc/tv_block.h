@@ -139,6 +139,22 @@ struct __attribute__((aligned(16))) FlatItem { u32 where, coordId, ntCells, pad;
 // stats[4..19] = per-class cell counts; the device header has room behind them: [STAT_TR_PATHS], [+ 1] = transition blocks of
 // the run through the table-driven body / that fell back to the general phases (GPU passes, vx_transition_path_counts)
 enum { STAT_TR_PATHS = 20 };
+// [STAT_MAT_PATHS], [+ 1] = material blocks of a full run that were voted / that were replayed from the material store
+// (vx_material_path_counts); [STAT_MAT_MISS] = a replayed block found no entry in the store (the host repeats the run as a voting one)
+enum { STAT_MAT_PATHS = 22, STAT_MAT_MISS = 24 };
+
+// The material store of one level >= 1 (GPU backend, vx_host.inl ensure_mat_store): what the material blocks of the last full
+// run on this grid left - cache, bitmap, cell count - by that run's own slot numbers, and the map from block coordinate to
+// those.  Everything in it is a function of the resident grid alone (lattice signs, cell map, BF_Empty flags, level-0
+// materials and blends): a full run on an unchanged grid copies a block's entry where it would vote again (k_main,
+// mat_copy_block).  Written by a capturing run (mat_block), read by replaying ones, touched by nothing else.
+struct MatStoreLevel {
+	int* index;         // [cnt^3] block coordinate id -> entry, -1 = none
+	u16* cache;         // [cap][4096]
+	u32* bits;          // [cap][128]
+	u16* cells;         // [cap]
+};
+
 struct Globals {
 	GridView grid;
 	const u8* emptyFlags;   // [cnt0^3] BF_Empty of every level-0 block (host-computed property of the Grid)
@@ -159,6 +175,8 @@ struct Globals {
 	// count from it, k_main's level-0 walk and level-1 material blocks its bitmap - nobody forms one
 	const u32* cellMap;               // [cnt0^3][128]
 	const u16* cellCount;             // [cnt0^3]
+	// full single-stream runs that capture into or replay from the material store (all null in every other run)
+	MatStoreLevel matStore[MAX_LEVELS];
 	PyramidLevel pyr[PYRAMID_LEVELS]; // [1..]: lattice copies of the distance field for the coarser levels (GPU backend)
 	XPlanes xp[XPLANE_LEVELS];        // yz-planes of the lattices 0..2 at every 32nd x (the x faces of the transition pass)
 	// full runs: blocks the fast regular passes (tv_fast0.h, tv_fast1.h) hand on to the general pass (a zero sample, a LOD

@@ -54,6 +54,7 @@
 
 #define VX_BACKEND_NAME "hip:gfx950"
 #define VX_BACKEND_CELL_MAP 1    // this backend keeps the cell map (MirrorState::cellMap; vx_host.inl ensure_cell_map, vx_grid_cell_map)
+#define VX_BACKEND_MAT_STORE 1   // this backend keeps the material store (MatStoreLevel; vx_host.inl ensure_mat_store, k_main's copy items)
 #define VX_BACKEND_HEADER_WAIT 1 // this backend times a run by the device clock and lets the host wait for the header (vx_host.inl RunClock)
 
 namespace {
@@ -1627,7 +1628,7 @@ template <bool GATED, bool PARTIAL = false, bool CELLMAP = false>
 // walks of its level-0 children would have left - bitmap, consistency bits, cell count, an empty record - and every block of a
 // level below emitFrom its own empty record (all seven meshes): the caches are complete for a later Modification, the lists
 // hold nothing of these levels.
-__device__ __forceinline__ void mat_block(const ExecParamsDev& p, u32 level, u32 slot, MatLds& st, const int tid, const bool selfChild = false, const u32* boxLo = nullptr, const u32* boxHi = nullptr, const u32 emitFrom = 0u)
+__device__ __forceinline__ void mat_block(const ExecParamsDev& p, u32 level, u32 slot, MatLds& st, const int tid, const bool selfChild = false, const u32* boxLo = nullptr, const u32* boxHi = nullptr, const u32 emitFrom = 0u, const bool capture = false)
 {
 	const LevelDesc& L = p.levels[level];
 	const LevelDesc& C = p.levels[level - 1];
@@ -1995,6 +1996,16 @@ __device__ __forceinline__ void mat_block(const ExecParamsDev& p, u32 level, u32
 	if (THROUGH) {
 		store16_through(cacheOut, (u32)tid * 16u, ((const uint4*)st.out)[tid]);
 		store16_through(cacheOut, (u32)(tid + WG) * 16u, ((const uint4*)st.out)[tid + WG]);
+		if (capture) {
+			// the material store: what this block leaves, at its slot, for the full runs behind this one on an unchanged grid
+			// (plain stores: only later launches read them)
+			const MatStoreLevel& S = p.G.matStore[level];
+			uint4* sc = (uint4*)(S.cache + (size_t)slot * BLOCK_CELLS);
+			sc[tid] = ((const uint4*)st.out)[tid];
+			sc[tid + WG] = ((const uint4*)st.out)[tid + WG];
+			if (tid < 32) ((uint4*)(S.bits + (size_t)slot * 128))[tid] = ((const uint4*)st.ntRow)[tid];
+			if (tid == 0) { S.cells[slot] = (u16)st.ntTotal; S.index[L.slotCoord[slot]] = (int)slot; }
+		}
 		publish_done_through(L.matDone + slot, p.G.epoch, st.ntTotal);
 	} else {
 		((uint4*)cacheOut)[tid] = ((const uint4*)st.out)[tid];
@@ -2002,10 +2013,51 @@ __device__ __forceinline__ void mat_block(const ExecParamsDev& p, u32 level, u32
 	}
 }
 
+// The same block replayed from the material store (k_main of a full single-stream run on a grid that has not changed since
+// the run that captured: MainPlan::matMode 2): everything mat_block<true, false, true> leaves - cache and bitmap through
+// write-through stores, cell count, the large-block count, the flat item, the flag - copied from the entry of the block's
+// coordinate.  No LDS, no samples, no children: a copy item waits for nobody.  A coordinate without an entry (cannot happen
+// on an unchanged grid) is never read through: the block leaves an empty cache and no cells, the flag all the same - nobody
+// waits for it in vain - and the header word that makes the host drop the store and repeat the run as a voting one.
+__device__ __forceinline__ void mat_copy_block(const ExecParamsDev& p, u32 level, u32 slot, const int tid)
+{
+	const auto uni = [](u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }; // (what every lane reads from one address)
+	const LevelDesc& L = p.levels[level];
+	const MatStoreLevel& S = p.G.matStore[level];
+	const u32 coord = uni(L.slotCoord[slot]);
+	const int src = (int)uni((u32)S.index[coord]);
+	const bool hit = src >= 0 && (u32)src < L.cap;
+	const u32 e2 = (u32)EMPTY_MATINFO | ((u32)EMPTY_MATINFO << 16);
+	uint4 c0 = make_uint4(e2, e2, e2, e2), c1 = c0, b = make_uint4(0, 0, 0, 0);
+	u32 cnt = 0;
+	if (hit) {
+		const uint4* sc = (const uint4*)(S.cache + (size_t)src * BLOCK_CELLS);
+		c0 = sc[tid]; c1 = sc[tid + WG];
+		if (tid < 32) b = ((const uint4*)(S.bits + (size_t)src * 128))[tid];
+		cnt = uni((u32)S.cells[src]);
+	}
+	u16* cacheOut = L.cache + (size_t)slot * BLOCK_CELLS;
+	if (tid < 32) store16_through(L.ntBits + (size_t)slot * 128, (u32)tid * 16u, b);
+	store16_through(cacheOut, (u32)tid * 16u, c0);
+	store16_through(cacheOut, (u32)(tid + WG) * 16u, c1);
+	if (tid == 0) {
+		L.ntCount[slot] = (u16)cnt;
+		if (cnt > (u32)LARGE_THRESHOLD) atomicAdd(p.G.largeBlocks, 1u);
+		if (!hit) atomicOr(&p.G.stats[STAT_MAT_MISS], 1u);
+		u32 before = 0;
+		for (u32 l = 1; l < level; ++l) before += p.G.slotCounts[l];
+		FlatItem e;
+		e.where = (level << 24) | slot; e.coordId = coord; e.ntCells = cnt; e.pad = 0;
+		p.G.flatItems[before + slot] = e;
+	}
+	publish_done_through(L.matDone + slot, p.G.epoch, cnt);
+}
+
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(6))) void k_material(ExecParamsDev p, u32 level)
 {
 	__shared__ MatLds st;
 	const u32 nItems = p.G.dirty ? p.G.workCount[level] : *p.levels[level].nActive;
+	if (!p.G.dirty && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&p.G.stats[STAT_MAT_PATHS], nItems); // (vx_material_path_counts: voted)
 	for (u32 it = blockIdx.x; it < nItems; it += gridDim.x) mat_block<false>(p, level, p.G.dirty ? p.G.workItems[level][it] : it, st, (int)threadIdx.x);
 }
 
@@ -3258,7 +3310,7 @@ struct Backend {
 	int device = 0;
 	bool ok = true;
 	// launch geometry knobs, read from the environment once when the context is created (tuning aids)
-	// Runtime knobs (read once per context).  Nine in all with VX_POOL_SLACK and VX_HOST_TIMING (vx_host.inl); each selects a path
+	// Runtime knobs (read once per context).  Ten in all with VX_POOL_SLACK and VX_HOST_TIMING (vx_host.inl); each selects a path
 	// that production runs reach through their data - dense surfaces, grids beyond 1024^3, blocks with zero samples - so that the
 	// tests can drive those paths on small fixtures (tests/test_gpu_parity.py::test_hip_runtime_knobs_select_equivalent_paths).
 	struct Tuning {
@@ -3270,6 +3322,7 @@ struct Backend {
 		u32 dirtyFused = 1;  // VX_DIRTY_FUSED=0: incremental runs as the chain of launches with work lists
 		u32 syncWait = 0;    // VX_SYNC_WAIT=1: a full run is waited for with hipStreamSynchronize where the default waits for its header (wait_published)
 		u32 cellMap = 1;     // VX_CELLMAP=0: no cell map - the level-0 blocks of a single-stream run form their own bitmaps, its level-1 material blocks their children's
+		u32 matStore = 1;    // VX_MATSTORE=0: no material store - every full run votes the material caches of the levels >= 1
 		// fixed since round 6 (were environment variables while they were being measured; profiles/HISTORY.md has the sweeps)
 		static constexpr u32 classifyRowGroup = 4, regWgsPerCu = 20, f1WgsPerCu = 20, foldBlocks = 65536, upWgsPerCu = 5, mainWgsPerCu = 4, mainBatch = 2, mainUpperNum = 1, mainUpperDen = 4;
 		bool fast0() const { return (fast & 1u) != 0; }
@@ -3304,6 +3357,7 @@ struct Backend {
 		tune.dirtyFused = env_u32("VX_DIRTY_FUSED", 1);
 		tune.syncWait = env_u32("VX_SYNC_WAIT", 0);
 		tune.cellMap = env_u32("VX_CELLMAP", 1);
+		tune.matStore = env_u32("VX_MATSTORE", 1);
 		hipDeviceProp_t prop;
 		if (hipGetDeviceProperties(&prop, device) == hipSuccess) cus = prop.multiProcessorCount;
 		if (!check(hipStreamCreateWithFlags(&ownStream, hipStreamNonBlocking), "hipStreamCreate")) { err = lastError; return false; }
@@ -3393,6 +3447,11 @@ struct Backend {
 	// Does a context with a grid of edge n keep the cell map?  Where its full runs can be single-stream ones (single_stream:
 	// the knobs as below, mirrors below 4 GiB).
 	bool wants_cell_map(u32 n) const { return tune.cellMap && tune.upper && tune.fast0() && tune.fast1() && tune.selfHead && !tune.forceWide && n <= 1024u; }
+	// ... and the material store?  Where it keeps the cell map: only the runs that read the map capture and replay.
+	bool wants_mat_store(u32 n) const { return tune.matStore && wants_cell_map(n); }
+	// what the host asks of the next k_main of the cell-map form (MainPlan::matMode), and what the last run_main launched: the
+	// host learns from it whether the attempt it accepts was one that captured or replayed
+	u32 matMode = 0, matModeUsed = 0;
 	// the cell map of the level-0 blocks [yb0, yb1) x [zb0, zb1) (all x) from the brick mirror and the sign summaries
 	void run_cell_map(const GridView& g, const MirrorState& ms, u32 yb0, u32 yb1, u32 zb0, u32 zb1)
 	{
@@ -3903,6 +3962,7 @@ struct Backend {
 		unsigned long long items = 0; // at most: one material item per block, one regular, one transition
 		for (u32 l = 1; l < levels; ++l) items += (unsigned long long)p.levels[l].cap * (1u + (l < plan.fastEnd ? 1u : 0u) + (p.levels[l].hasTransitions ? 1u : 0u));
 		if (withLevel0) items += p.levels[0].cap;
+		matModeUsed = 0;
 		if (!items) return;
 		// persistent workgroups; without the level-0 queue at most as many as the previous run had items (the host's hint; any
 		// number is correct - a workgroup that finds the queues empty leaves - but every workgroup costs a dequeue)
@@ -3912,9 +3972,11 @@ struct Backend {
 			// (no level-0 queue: the persistent workgroups are the upper queue's)
 			plan.level0 = 0u; plan.upperNum = plan.upperDen = 1u; plan.emitFrom = emitFrom;
 			launch_with_event(k_main<false, true>, dim3(grid), UP_TAB_LDS + MAIN_STATE_LDS, dev(p), plan);
-		} else if (withLevel0 && p.G.cellMap)
+		} else if (withLevel0 && p.G.cellMap) {
+			plan.matMode = p.G.matStore[1].index ? matMode : 0u;
+			matModeUsed = plan.matMode;
 			launch_with_event(k_main<false, false, true>, dim3(grid), UP_TAB_LDS + MAIN_STATE_LDS, dev(p), plan);
-		else
+		} else
 			launch_with_event(k_main<false>, dim3(grid), UP_TAB_LDS + (withLevel0 ? MAIN_STATE_LDS : UP_STATE_LDS), dev(p), plan);
 		check(hipGetLastError(), "k_main launch");
 	}

@@ -77,6 +77,15 @@ struct vx_ctx {
 	// stale = a byte of the distance mirror or a sign summary has been written since it was built (ensure_cell_map)
 	void *dCellMap = nullptr, *dCellCount = nullptr;
 	bool cellMapStale = true;
+	// The material store (MatStoreLevel, tv_block.h; backends with VX_BACKEND_MAT_STORE): allocated by the first run that
+	// captures, freed with the level tables.  valid = a full single-stream run has filled it for the levels below
+	// matStoreLevels and nothing its contents depend on has changed since - distances, materials, blends, BF_Empty flags,
+	// the rank's range (mat_store_invalidate sits beside every cellMapStale = true and in the entry points that write
+	// materials or flags alone).
+	MatStoreLevel matStore[MAX_LEVELS] = {};
+	std::vector<void*> matStoreAllocs;
+	bool matStoreValid = false;
+	u32 matStoreLevels = 0;
 	void* dListCounts = nullptr;                         // listed blocks per LIST_WG block coordinates, all levels (LevelDesc::listCounts)
 	// Two sets of what a full run needs in its start state - the header's counters, the block -> slot maps of the levels >= 1,
 	// the list counts: a run works on one set, and its last kernel (k_tail) resets the other for the run behind it, which then
@@ -224,15 +233,22 @@ u32 ref_levels(u32 n)
 	return l + 1; // TransVoxelImpl.cpp:490
 }
 
+void mat_store_invalidate(vx_ctx* c) { c->matStoreValid = false; }
+
 void free_level_tables(vx_ctx* c)
 {
 	for (void* p : c->levelAllocs) c->be.free(p);
 	c->levelAllocs.clear();
+	for (void* p : c->matStoreAllocs) c->be.free(p);
+	c->matStoreAllocs.clear();
+	memset(c->matStore, 0, sizeof(c->matStore));
+	mat_store_invalidate(c);
 	c->tablesN = 0;
 }
 
 void release_grid(vx_ctx* c)
 {
+	mat_store_invalidate(c);
 	if (c->ownsGrid || c->ownsSlab) {
 		c->be.free(c->dDist); c->be.free(c->dMat); c->be.free(c->dBlend); c->be.free(c->dFlags);
 	}
@@ -250,6 +266,7 @@ void free_bricks(vx_ctx* c)
 	c->be.free(c->dCellMap); c->dCellMap = nullptr;
 	c->be.free(c->dCellCount); c->dCellCount = nullptr;
 	c->cellMapStale = true;
+	mat_store_invalidate(c);
 	c->brickN = 0;
 	c->bricksStale = true;
 }
@@ -323,6 +340,7 @@ bool ensure_bricks(vx_ctx* c)
 		c->be.run_rebrick(resident_view(c), dr, mr, mirror_state(c), box, nullptr, 0);
 		c->bricksStale = false;
 		c->cellMapStale = true;
+		mat_store_invalidate(c);
 	}
 	return true;
 }
@@ -346,6 +364,7 @@ void ensure_cell_map(vx_ctx* c)
 // wait for a full copy anyway (the rows of a halo exchange are written into the mirrors by its unpack kernel)
 void rebrick_blocks(vx_ctx* c, const u32* dIds, u32 count)
 {
+	mat_store_invalidate(c); // (every device edit passes here: distances, materials or blends of the listed blocks have changed, and their flags)
 	if (!c->be.wants_bricks() || c->bricksStale || !c->dBrick[0] || !count) return;
 	int dr[4], mr[4];
 	resident_ranges(c, dr, mr);
@@ -481,6 +500,33 @@ bool ensure_level_tables(vx_ctx* c)
 	select_run_set(c, 0);
 	return true;
 }
+
+#if defined(VX_BACKEND_MAT_STORE)
+// The material store, sized like the level tables it shadows (LevelDesc::slotOf, ::cache): allocated by the first run that
+// captures - a context whose full runs never take the single-stream form never pays for it.  Memory is touched only where
+// a captured block has a slot: 8.5 KB per active block of a level >= 1 (26 MB on the 1024^3 bench terrain).
+bool ensure_mat_store(vx_ctx* c)
+{
+	if (!c->be.wants_mat_store(c->n) || c->refLevels < 2) return false;
+	if (c->matStore[1].index) return true;
+	bool ok = true;
+	for (u32 L = 1; L < c->refLevels && L < MAX_LEVELS && ok; ++L) {
+		const LevelDesc& d = c->lv[L];
+		const size_t total = (size_t)d.cnt * d.cnt * d.cnt, cap = d.cap ? d.cap : 1;
+		void* a[4] = { c->be.alloc(total * 4), c->be.alloc(cap * BLOCK_CELLS * 2), c->be.alloc(cap * 512), c->be.alloc(cap * 2 + 16) };
+		for (void* q : a) { if (q) c->matStoreAllocs.push_back(q); else ok = false; }
+		MatStoreLevel& S = c->matStore[L];
+		S.index = (int*)a[0]; S.cache = (u16*)a[1]; S.bits = (u32*)a[2]; S.cells = (u16*)a[3];
+	}
+	if (!ok) { // (no store: the runs vote, as they do with VX_MATSTORE=0)
+		for (void* q : c->matStoreAllocs) c->be.free(q);
+		c->matStoreAllocs.clear();
+		memset(c->matStore, 0, sizeof(c->matStore));
+	}
+	mat_store_invalidate(c);
+	return ok;
+}
+#endif
 
 bool ensure_pools(vx_ctx* c, u32 needVerts, u32 needIdx)
 {
@@ -1212,6 +1258,7 @@ int vx_grid_invalidate(vx_ctx* c)
 	// the caller rewrote attached memory in place: the brick mirrors, lattice copies and sign summaries are rebuilt by the
 	// next polygonization, and whatever surface the context holds no longer describes the grid
 	c->bricksStale = true;
+	mat_store_invalidate(c);
 	c->haveSurface = false;
 	return VX_OK;
 }
@@ -1343,6 +1390,7 @@ void refresh_halo_layers(vx_ctx* c)
 	const int yb0 = (int)c->brickYb0, yb1 = yb0 + (int)c->brickRowsY, zb0 = (int)c->brickZb0, zb1 = zb0 + (int)c->brickPlanesZ;
 	const int own0 = (int)(alongY ? c->yBegin : c->zBegin) / 16, own1 = (int)(alongY ? c->yEnd : c->zEnd) / 16;
 	c->cellMapStale = true;
+	mat_store_invalidate(c);
 	auto layers = [&](int l0, int l1) {
 		if (l1 <= l0) return;
 		const int box[4] = { alongY ? l0 : yb0, alongY ? l1 : yb1, alongY ? zb0 : l0, alongY ? zb1 : l1 };
@@ -1406,6 +1454,7 @@ int vx_halo_exchange(vx_ctx* c)
 	if (!ok) return fail(c, VX_ERR_DEVICE, "vx_halo_exchange: " + c->be.error());
 	c->be.run_halo_moves(pl.hasLo ? &pl.recvLo : nullptr, pl.hasHi ? &pl.recvHi : nullptr, halo_view(c), mirror_state(c), alongY);
 	c->cellMapStale = true; // (the unpack writes the received rows into the bricks: the cells of the last owned block layer read them)
+	mat_store_invalidate(c); // (... and the received flags and material rows are what the votes of that layer read)
 	refresh_halo_layers(c);
 	c->haveSurface = false;
 	return VX_OK;
@@ -1439,6 +1488,7 @@ int vx_halo_exchange_group(vx_ctx* const* ctxs, int count)
 		if (!c->be.sync_ok()) return fail(c, VX_ERR_DEVICE, "vx_halo_exchange_group: copy failed: " + c->be.error());
 		c->be.run_halo_moves(plans[(size_t)i].hasLo ? &plans[(size_t)i].recvLo : nullptr, plans[(size_t)i].hasHi ? &plans[(size_t)i].recvHi : nullptr, halo_view(c), mirror_state(c), c->slabAxis == 2);
 		c->cellMapStale = true;
+		mat_store_invalidate(c);
 		refresh_halo_layers(c);
 		c->haveSurface = false;
 	}
@@ -1453,6 +1503,7 @@ int vx_grid_update_blocks(vx_ctx* c, uint32_t count, const uint32_t* ids, const 
 	const u32 n = c->n, nb = n / 16;
 	bool ok = true;
 	for (u32 i = 0; i < count; ++i) if (ids[i] >= nb * nb * nb) return fail(c, VX_ERR_INVALID, "vx_grid_update_blocks: block id out of range");
+	mat_store_invalidate(c); // (also where only the flags change: the skip flags of level-0 blocks mask their cells out of the votes)
 	if (count && (dist || mat || blend)) {
 		// the blocks travel as they are (4096 contiguous bytes each) and are scattered into the dense fields on the device
 		const size_t bytes = (size_t)count * 4096;
@@ -1639,6 +1690,25 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 			p.G.cellMap = (const u32*)c->dCellMap; p.G.cellCount = (const u16*)c->dCellCount;
 		}
 #endif
+#if defined(VX_BACKEND_MAT_STORE)
+		// The same runs - and only they - capture into the material store or replay from it.  Replay: the store is valid (nothing
+		// it depends on has changed since a run filled it) and covers the run's levels.  Otherwise this attempt captures: the store
+		// is invalid from here on and becomes valid again behind the loop, when the attempt that was accepted is known to have
+		// been a capturing one (its header arrived without HDR_GIVEUP: every material item has completed).
+		c->be.matMode = c->be.matModeUsed = 0; // (matModeUsed: set by the launch of k_main's cell-map form, if this attempt has one)
+		if (p.G.cellMap && ensure_mat_store(c)) {
+			const bool replay = c->matStoreValid && levels <= c->matStoreLevels;
+			if (!replay) {
+				mat_store_invalidate(c);
+				for (u32 L = 1; L < levels; ++L) {
+					const size_t total = (size_t)c->lv[L].cnt * c->lv[L].cnt * c->lv[L].cnt;
+					if (!c->be.fill(c->matStore[L].index, 0xFF, total * 4)) return fail(c, VX_ERR_DEVICE, "vx_polygonize: material store reset failed");
+				}
+			}
+			for (u32 L = 1; L < levels; ++L) p.G.matStore[L] = c->matStore[L];
+			c->be.matMode = replay ? 2u : 1u;
+		}
+#endif
 		// device time: two clock words of the header on the single-stream path; the event pair on the chain of launches, with
 		// stage timing and under VX_HOST_TIMING (a recorded event is a packet of its own in the stream: ~8 us before the next kernel)
 		const bool byClock = !hostTiming && RunClock::applies(c->be, p, levels);
@@ -1718,6 +1788,10 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 		t3 = tNow();
 		const u32 usedV = c->hdr[HDR_CURSORS], usedI = c->hdr[HDR_CURSORS + CUR_I], overflow = c->hdr[HDR_CURSORS + CUR_OVF];
 		if (c->hdr[HDR_GIVEUP]) return fail(c, VX_ERR_DEVICE, "vx_polygonize: a dependency wait inside the upper pass timed out (internal error)");
+#if defined(VX_BACKEND_MAT_STORE)
+		// a replayed block without an entry in the store (an unchanged grid has none): the store is dropped, the run repeated as a voting one
+		if (c->be.matModeUsed == 2u && c->hdr[HDR_STATS + STAT_MAT_MISS]) { mat_store_invalidate(c); c->be.matModeUsed = 0; continue; }
+#endif
 		if (c->hdr[HDR_LARGE] && !c->be.largeClass) { c->be.largeClass = true; continue; } // blocks of the large class showed up: once more, with it
 		if (!overflow) break;
 		if (++retries > 3) return fail(c, VX_ERR_OVERFLOW, "vx_polygonize: output pools keep overflowing");
@@ -1725,6 +1799,10 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 		if (!ensure_pools(c, usedV + usedV / 8 + 1024, usedI + usedI / 8 + 4096)) return fail(c, VX_ERR_OVERFLOW, "vx_polygonize: cannot grow output pools");
 	}
 	c->be.emitFrom = 0;
+#if defined(VX_BACKEND_MAT_STORE)
+	if (c->be.matModeUsed == 1u) { c->matStoreValid = true; c->matStoreLevels = levels; } // (the accepted attempt captured)
+	c->be.matMode = c->be.matModeUsed = 0;
+#endif
 	c->largeHint = c->hdr[HDR_LARGE] != 0;
 	{
 		// what the next run of this context can expect on the levels >= 1 (sizes the launch of k_main): a material item per
@@ -2454,6 +2532,14 @@ int vx_stats(vx_ctx* c, uint32_t stats[20])
 	VX_ENTER_RUN(c); // (the host's copy of the header: nothing a run in flight touches)
 	if (!c || !c->haveSurface) return fail(c, VX_ERR_INVALID, "vx_stats: nothing polygonized yet");
 	memcpy(stats, c->stats, 80);
+	return VX_OK;
+}
+
+int vx_material_path_counts(vx_ctx* c, uint32_t out[2])
+{
+	VX_ENTER_RUN(c); // (the host's copy of the header)
+	if (!c || !out || !c->haveSurface) return fail(c, VX_ERR_INVALID, "vx_material_path_counts: nothing polygonized yet");
+	out[0] = c->hdr[HDR_STATS + STAT_MAT_PATHS]; out[1] = c->hdr[HDR_STATS + STAT_MAT_PATHS + 1];
 	return VX_OK;
 }
 

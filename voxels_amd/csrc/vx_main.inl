@@ -22,6 +22,9 @@
 //     for its own material behind the request of its lattice samples, a transition block for it behind planes,
 //     classification and scans.  The flags are LevelDesc::matDone (publish_done_through / wait_done: write-through stores and
 //     loads, placement-independent, every wait bounded).
+//     On a grid that has not changed since a full run of this form filled the material store (MatStoreLevel, tv_block.h;
+//     MainPlan::matMode) the material items are copy items (mat_copy_block): same queue position, same stores, same flag -
+//     the regular and transition items behind them notice nothing - but no samples, no vote and nobody to wait for.
 //   * the level-0 queue: the active level-0 slots, taken in batches of consecutive slots (x-neighbour blocks: a batch is
 //     walked with the register prefetch of f0_walk, and its blocks share halo lines in one XCD's L2).
 // A workgroup prefers one of the queues (a share of the workgroups the upper one, so that the latency-bound dependency chain
@@ -58,6 +61,10 @@ struct MainPlan {
 	// transition items only for the levels >= emitFrom
 	u32 emitFrom;
 	u32 trTables;   // 1: transition blocks take the table-driven body where they qualify (VX_FAST bit 2; vx_fastt.inl)
+	// the material store (MAP form only; Globals::matStore is set for the run's levels where this is not 0): 1 = the material
+	// blocks vote as always and also leave their results in the store (mat_block: capture), 2 = they are copy items
+	// (mat_copy_block).  Uniform at run time: not another instantiation of the kernel.
+	u32 matMode;
 };
 
 // DIRTY: the incremental run's form (TransVoxelRun::Execute with a Modification, src/TransVoxelImpl.cpp:429-465): the same two
@@ -150,9 +157,10 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 				if (level >= plan.fastEnd && tid0 == 0) p.G.slowItems[1][atomicAdd(&p.G.slowCount[1], 1u)] = (level << 24) | slot;
 			} else if (PARTIAL)
 				mat_block<true, true>(p, level, slot, *(MatLds*)state, tid, true, nullptr, nullptr, plan.emitFrom);
-			else if (MAP)
-				mat_block<true, false, true>(p, level, slot, *(MatLds*)state, tid, true);
-			else
+			else if (MAP) {
+				if (plan.matMode == 2u) { mat_copy_block(p, level, slot, tid); continue; }
+				mat_block<true, false, true>(p, level, slot, *(MatLds*)state, tid, true, nullptr, nullptr, 0u, plan.matMode == 1u);
+			} else
 				mat_block<true>(p, level, slot, *(MatLds*)state, tid, plan.level0 != 0u);
 			continue;
 		}
@@ -176,6 +184,9 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 		asm volatile("" : "+v"(tid)); // (the address is formed here, not carried through the kernel)
 		// (no item of this kernel counts into the words 2 and 3: they hold the transition blocks by body, STAT_TR_PATHS)
 		if (tid < 20 && wgStats[tid]) atomicAdd(&p.G.stats[(tid == 2 || tid == 3) ? (int)STAT_TR_PATHS + tid - 2 : tid], wgStats[tid]);
+		// full runs: the material blocks by body (vx_material_path_counts).  Which body is the launch's (plan.matMode), so the
+		// count is the length of the queue's material segment, added once - a counter per item would be kept by every workgroup
+		if (!DIRTY && blockIdx.x == 0 && tid == 20 && matTotal) atomicAdd(&p.G.stats[STAT_MAT_PATHS + ((MAP && plan.matMode == 2u) ? 1 : 0)], matTotal);
 	}
 }
 
