@@ -429,6 +429,88 @@ int vx_grid_walk_field(vx_ctx* ctx, const vx_walk_query* query, const vx_walk_go
                        uint32_t* d_field /* device, may be NULL */, uint8_t* d_dirs /* device, may be NULL */,
                        vx_walk_counts* counts);
 
+/* ---- undo records (HIP library only) ----------------------------------------------------------------------------------
+ * Every edit of the resident grid - vx_grid_inject_ball / _material / _brushes, vx_grid_smooth, vx_grid_islands with
+ * VX_ISLANDS_REMOVE - is destructive.  An undo record is a device-resident copy of a set of whole 16^3 grid blocks, byte for
+ * byte, owned by the context that made it: CAPTURE the blocks an edit may touch, edit, TRIM the record to the blocks the edit
+ * did change, and SWAP it with the grid to take the edit back.  A swap exchanges, so the same record is the undo of the edit,
+ * then its redo, then its undo again; a stack of records is an undo history.  The edit entry points do not capture by
+ * themselves.  voxels_amd/csrc/tv_undo.h is the per-block logic; tests/undo_oracle.py states this text again in numpy.
+ * Boxes are voxel boxes [lo, hi) in grid coordinates, internal axes (Z up), as vx_island_query; block ids number the blocks as
+ * vx_grid_read_block does: (bz * nb + by) * nb + bx, nb = n / 16.
+ *   Capture    vx_grid_capture: the record holds every block that at least one box intersects - block coordinates lo / 16 ..
+ *              (hi - 1) / 16 per axis - each once, in ascending id, whatever the order or the overlap of the boxes.  Per block
+ *              it holds the 4096 distances, 4096 materials and 4096 blends as the dense fields hold them (the mirrors play no
+ *              part) and the block's BF_Empty byte as the grid's flag array holds it: the flag is stored, not recomputed - a
+ *              block that only material brushes touched keeps its flag, and vx_grid_upload takes flags from the caller, so the
+ *              flag is not a function of the voxels.  count = 0 gives a valid empty record.  More than VX_RECORD_MAX_BLOCKS
+ *              distinct blocks is VX_ERR_INVALID.  The call never changes the grid, the flags or the mirrors, and a full run
+ *              afterwards replays what it replayed before.
+ *   Trim       vx_record_trim compares every held block with the grid as it is now, drops the blocks whose 12 288 bytes and
+ *              flag byte are all equal and packs the rest, in their order, into a right-sized allocation; *dropped (may be
+ *              NULL) receives the number of blocks dropped.  Legal at any time, also after swaps.  Never changes the grid.
+ *   Swap       vx_record_swap: for every held block the grid receives the record's three fields and flag byte and the record
+ *              receives what the grid held.  The brick mirrors follow, as after any edit: a polygonization after the call needs
+ *              no vx_grid_invalidate.  result (may be NULL) receives
+ *                out_min / out_max   the box of the voxels that differed in distance, material or blend, in the convention of
+ *                                    vx_grid_islands and vx_grid_smooth: output order (x, z, y), floats; for differing voxels
+ *                                    spanning a..b inclusive per internal axis it is [a, b + 1] clamped to [0, n]; zeros when no
+ *                                    voxel differed.  Feed it to vx_polygonize_dirty - no margin is needed, also where only
+ *                                    materials or blends differed.
+ *                changed_voxels      the number of those voxels
+ *                changed_blocks      blocks with such a voxel or a different flag byte
+ *                flag_changes        blocks whose BF_Empty byte differed (such a block counts as changed and moves no box)
+ *              A swap of an empty record, or of a record equal to the grid, is VX_OK, returns zeros, and a full run afterwards
+ *              replays what it replayed before.
+ *   Reading    vx_record_info_get; vx_record_block_ids (the held ids, ascending; capacity >= the block count);
+ *              vx_record_read_block (entry `index` in the layout of vx_grid_read_block: rows z-major, 16 bytes each; every
+ *              output may be NULL).
+ *   Brushes    vx_brush_box (host only, no context): the voxel box [16 * first, 16 * (first + cnt)) per internal axis of the
+ *              blocks the position -+ extents block test of the edits finds for the brush - the same float32 expressions per
+ *              block and axis - for a grid of edge n.  1 = the brush touches the grid, 0 = it misses it (the box is zeroed:
+ *              leave it out).  Capturing the boxes of a brush array captures exactly the blocks vx_grid_inject_brushes touches.
+ *   Lifetime   vx_record_free releases a record (NULL is legal); vx_ctx_destroy frees what is left.  A record survives full
+ *              and incremental runs, vx_compact_pools and further edits; it can be used while the context owns a whole grid
+ *              of the edge it was captured from.
+ * Everything is checked before anything is launched: VX_ERR_INVALID, with nothing changed, for a null context, record, out
+ * pointer or info, a null box array with count > 0, count > VX_RECORD_MAX_BOXES, lo >= hi or hi > n on any axis, a context
+ * that does not own a whole grid (vx_grid_upload / vx_grid_upload_packed; capture, trim, swap), a record made by another
+ * context, a record whose n differs from the context's grid now (trim, swap), an index or a capacity out of range.
+ * vx_brush_box returns VX_ERR_INVALID for a null argument or an n that is not a multiple of 16 in 16..2048.  VX_ERR_DEVICE,
+ * with the grid untouched, when memory cannot be allocated.
+ * All calls are synchronous and run on the context's stream (vx_set_stream).  Capture waits for the device once: the number of
+ * distinct blocks sizes the allocation.  Trim waits once: the kept count sizes the new allocation (the one it replaces is
+ * released behind the next wait of one of these calls, or with the context).  Swap waits once, at its end, for the result.
+ * Memory: 12 293 bytes of device memory per held block - 12 288 of fields, 1 flag, 4 id - in one allocation per record, rounded
+ * as the allocator rounds; vx_record_info.bytes is that product.  Working memory, kept with the context and only ever grown:
+ * one bit and 4 bytes per 32 blocks of the grid (capture) or of the record (trim), 24 bytes per box, 4 bytes per held block. */
+typedef struct vx_record vx_record;                 /* opaque; belongs to the context that made it */
+typedef struct vx_box { uint32_t lo[3], hi[3]; } vx_box;         /* 24 bytes; [lo, hi), grid coordinates, internal axes (Z up) */
+typedef struct vx_record_info {                                   /* 48 bytes */
+    uint32_t n, blocks;            /* grid edge at capture; blocks held now */
+    uint64_t bytes;                /* device memory held now */
+    uint32_t min[3], max[3];       /* block coordinates of the held blocks, inclusive; zeros when blocks == 0 */
+    uint32_t swaps, reserved;      /* successful vx_record_swap calls so far */
+} vx_record_info;
+typedef struct vx_swap_result {                                   /* 48 bytes */
+    float    out_min[3], out_max[3];
+    uint64_t changed_voxels;       /* voxels that differed in distance, material or blend */
+    uint32_t changed_blocks;       /* blocks with such a voxel or a different flag byte */
+    uint32_t flag_changes;         /* blocks whose BF_Empty byte differed */
+    uint64_t reserved;
+} vx_swap_result;
+#define VX_RECORD_MAX_BLOCKS (1u << 18)   /* a whole 1024^3 grid */
+#define VX_RECORD_MAX_BOXES  (1u << 16)
+int  vx_grid_capture(vx_ctx* ctx, const vx_box* boxes /* host */, uint32_t count, vx_record** out);
+int  vx_record_trim(vx_ctx* ctx, vx_record* record, uint32_t* dropped /* may be NULL */);
+int  vx_record_swap(vx_ctx* ctx, vx_record* record, vx_swap_result* result /* may be NULL */);
+int  vx_record_info_get(vx_ctx* ctx, const vx_record* record, vx_record_info* info);
+int  vx_record_block_ids(vx_ctx* ctx, const vx_record* record, uint32_t* ids, uint32_t capacity);
+int  vx_record_read_block(vx_ctx* ctx, const vx_record* record, uint32_t index, int8_t* dist, uint8_t* mat, uint8_t* blend,
+                          uint8_t* empty_flag);
+void vx_record_free(vx_ctx* ctx, vx_record* record);
+int  vx_brush_box(const vx_brush* brush, uint32_t n, vx_box* out);
+
 /* MaterialMap::GetMaterial resolved on the host (include/MaterialMap.h:19-30): lut[id] = {DiffuseIds0[3],
  * DiffuseIds1[3]}, valid[id] == 0 means GetMaterial returned NULL (texture bytes stay 0). */
 int vx_material_lut(vx_ctx* ctx, const uint8_t* lut /*256*6*/, const uint8_t* valid /*256*/);

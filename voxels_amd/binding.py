@@ -60,6 +60,15 @@ WALK_GOAL_DTYPE = np.dtype([("x", "<u4"), ("y", "<u4"), ("z", "<u4"), ("cost", "
 WALK_COUNTS_DTYPE = np.dtype([("standable", "<u8"), ("reached", "<u8"), ("goals_used", "<u4"), ("goals_ignored", "<u4"),
                               ("max_distance", "<u4"), ("sweeps", "<u4")])
 assert WALK_QUERY_DTYPE.itemsize == 64 and WALK_GOAL_DTYPE.itemsize == 16 and WALK_COUNTS_DTYPE.itemsize == 32
+
+# undo records (include/voxels_hip.h, "undo records")
+BOX_DTYPE = np.dtype([("lo", "<u4", 3), ("hi", "<u4", 3)])
+RECORD_INFO_DTYPE = np.dtype([("n", "<u4"), ("blocks", "<u4"), ("bytes", "<u8"), ("min", "<u4", 3), ("max", "<u4", 3), ("swaps", "<u4"), ("reserved", "<u4")])
+SWAP_RESULT_DTYPE = np.dtype([("out_min", "<f4", 3), ("out_max", "<f4", 3), ("changed_voxels", "<u8"), ("changed_blocks", "<u4"), ("flag_changes", "<u4"),
+                              ("reserved", "<u8")])
+assert BOX_DTYPE.itemsize == 24 and RECORD_INFO_DTYPE.itemsize == 48 and SWAP_RESULT_DTYPE.itemsize == 48
+RECORD_MAX_BLOCKS = 1 << 18
+RECORD_MAX_BOXES = 1 << 16
 SPHERE_STARTED_IN_CONTACT = 1
 # vx_lod_params / vx_lod_draw / vx_draw_indexed / vx_lod_counts (include/voxels_hip.h, LOD selection)
 LOD_PARAMS_DTYPE = np.dtype([("camera", "<f4", 3), ("n_planes", "<u4"), ("planes", "<f4", (6, 4)), ("ranges", "<f4", 16)])
@@ -288,6 +297,21 @@ class HipLibrary:
         if self.has_walk_field:
             lib.vx_grid_walk_field.argtypes = [vp, vp, vp, u32, vp, vp, vp]
             lib.vx_grid_walk_field.restype = C.c_int
+        # undo records: HIP builds only, likewise
+        self.has_undo = all(hasattr(lib, name) for name in ("vx_grid_capture", "vx_record_trim", "vx_record_swap", "vx_record_info_get", "vx_record_block_ids",
+                                                            "vx_record_read_block", "vx_record_free", "vx_brush_box"))
+        if self.has_undo:
+            lib.vx_grid_capture.argtypes = [vp, vp, u32, C.POINTER(vp)]
+            lib.vx_record_trim.argtypes = [vp, vp, vp]
+            lib.vx_record_swap.argtypes = [vp, vp, vp]
+            lib.vx_record_info_get.argtypes = [vp, vp, vp]
+            lib.vx_record_block_ids.argtypes = [vp, vp, vp, u32]
+            lib.vx_record_read_block.argtypes = [vp, vp, u32, vp, vp, vp, vp]
+            lib.vx_record_free.argtypes = [vp, vp]
+            lib.vx_record_free.restype = None
+            lib.vx_brush_box.argtypes = [vp, u32, vp]
+            for name in ("vx_grid_capture", "vx_record_trim", "vx_record_swap", "vx_record_info_get", "vx_record_block_ids", "vx_record_read_block", "vx_brush_box"):
+                getattr(lib, name).restype = C.c_int
         self.has_lod = hasattr(lib, "vx_lod_select")
         if self.has_lod:
             lib.vx_lod_select_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
@@ -349,6 +373,33 @@ def smooth_op(box, center=None, radius=0.0, strength=1.0, iterations=1):
     return op
 
 
+def boxes(rows):
+    """a BOX_DTYPE array from one, or from rows of (lo, hi) in grid coordinates (internal axes, Z up)"""
+    if isinstance(rows, np.ndarray) and rows.dtype == BOX_DTYPE:
+        return np.ascontiguousarray(rows).reshape(-1)
+    b = np.zeros(len(rows), BOX_DTYPE)
+    for k, (lo, hi) in enumerate(rows):
+        b[k]["lo"], b[k]["hi"] = np.asarray(lo, np.uint32), np.asarray(hi, np.uint32)
+    return b
+
+
+def brush_boxes(brushes, n, library=None):
+    """vx_brush_box over a BRUSH_DTYPE array: the BOX_DTYPE array of the brushes that touch a grid of edge n, in array order -
+    capture it before vx_grid_inject_brushes and the record holds exactly the blocks the batch touches"""
+    L = library or HipLibrary()
+    if not L.has_undo:
+        raise VoxelsHipError("this library has no undo records (HIP builds only)")
+    brushes = np.ascontiguousarray(brushes, BRUSH_DTYPE).reshape(-1)
+    out = np.zeros(brushes.size, BOX_DTYPE)
+    keep = np.zeros(brushes.size, bool)
+    for k in range(brushes.size):
+        rc = L.lib.vx_brush_box(_ptr(brushes[k:k + 1]), int(n), _ptr(out[k:k + 1]))
+        if rc < 0:
+            raise VoxelsHipError("vx_brush_box failed (%d)" % rc)
+        keep[k] = rc == 1
+    return out[keep]
+
+
 def capsule_stroke(p0, p1, radius, inj_type=2, margin=2.0):
     """One capsule brush for a tool of `radius` moved from p0 to p1 (grid coordinates, Z up): positioned at the middle of the
     segment, the ends relative to it, rewriting the segment's box grown by radius + margin on every side."""
@@ -373,6 +424,61 @@ class Level:
 
     def totals(self):
         return (len(self.infos), len(self.verts), len(self.idx), len(self.tverts), len(self.tidx))
+
+
+class Record:
+    """An undo record (include/voxels_hip.h, "undo records") of a Polygonizer: made by Polygonizer.capture, freed by free() or
+    when it is collected while the polygonizer that owns it lives."""
+
+    def __init__(self, poly, handle):
+        self._p, self._r = poly, handle
+
+    def _call(self, fn, *args):
+        if not self._r:
+            raise VoxelsHipError("the record has been freed")
+        p = self._p
+        p._check(getattr(p._lib, fn)(p._h, self._r, *args), fn)
+
+    def trim(self):
+        """vx_record_trim -> the number of blocks dropped"""
+        dropped = C.c_uint32()
+        self._call("vx_record_trim", C.byref(dropped))
+        return int(dropped.value)
+
+    def swap(self):
+        """vx_record_swap -> the SWAP_RESULT_DTYPE record"""
+        res = np.zeros(1, SWAP_RESULT_DTYPE)
+        self._call("vx_record_swap", _ptr(res))
+        return res[0]
+
+    def info(self):
+        """vx_record_info_get -> the RECORD_INFO_DTYPE record"""
+        info = np.zeros(1, RECORD_INFO_DTYPE)
+        self._call("vx_record_info_get", _ptr(info))
+        return info[0]
+
+    def block_ids(self):
+        """vx_record_block_ids -> the held block ids, ascending"""
+        ids = np.zeros(int(self.info()["blocks"]), np.uint32)
+        self._call("vx_record_block_ids", _ptr(ids) if ids.size else None, ids.size)
+        return ids
+
+    def read_block(self, index):
+        """(dist int8[16,16,16] (z,y,x), mat, blend, BF_Empty) of entry `index`, as Polygonizer.read_block"""
+        d = np.zeros((16, 16, 16), np.int8)
+        m = np.zeros((16, 16, 16), np.uint8)
+        b = np.zeros((16, 16, 16), np.uint8)
+        f = np.zeros(1, np.uint8)
+        self._call("vx_record_read_block", int(index), _ptr(d), _ptr(m), _ptr(b), _ptr(f))
+        return d, m, b, int(f[0])
+
+    def free(self):
+        if self._r and getattr(self._p, "_h", None):
+            self._p._lib.vx_record_free(self._p._h, self._r)
+        self._r = None
+
+    def __del__(self):
+        self.free()
 
 
 class Polygonizer:
@@ -498,6 +604,15 @@ class Polygonizer:
         self._check(self._lib.vx_grid_smooth(self._h, _ptr(ops) if ops.size else None, ops.size, _ptr(results) if ops.size else None,
                                              _ptr(mn), _ptr(mx), C.byref(changed)), "vx_grid_smooth")
         return results, mn, mx, int(changed.value)
+
+    def capture(self, box_rows):
+        """vx_grid_capture: the blocks that a BOX_DTYPE array (or rows of (lo, hi)) intersects -> a Record"""
+        if not self._L.has_undo:
+            raise VoxelsHipError("this library has no undo records (HIP builds only)")
+        b = boxes(box_rows)
+        h = C.c_void_p()
+        self._check(self._lib.vx_grid_capture(self._h, _ptr(b) if b.size else None, b.size, C.byref(h)), "vx_grid_capture")
+        return Record(self, h)
 
     def islands(self, box=None, detached_only=False, remove=False, anchor_faces=0x3F, max_voxels=0, air_value=127, labels=None, capacity=None):
         """vx_grid_islands: the connected components of the solid voxels of `box` ((lo, hi), None = the whole grid) ->

@@ -20,7 +20,7 @@ def _newer(target, sources):
 def build_hip(force=False, verbose=True):
     """hipcc --offload-arch=gfx950 ... -o voxels_amd/csrc/libvoxels_hip.so (cross-compiles without a GPU)."""
     out = os.path.join(CSRC, "libvoxels_hip.so")
-    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_walk.inl", "tv_walk.h", "vx_lod.inl", "tv_lod.h", "vx_scatter.inl", "tv_scatter.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
+    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_walk.inl", "tv_walk.h", "vx_undo.inl", "tv_undo.h", "vx_lod.inl", "tv_lod.h", "vx_scatter.inl", "tv_scatter.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
     srcs.append(os.path.join(ROOT, "include", "voxels_hip.h"))
     if not force and not _newer(out, srcs):
         return out
@@ -41,7 +41,8 @@ def build_hip(force=False, verbose=True):
                            "k_isl_local", "k_isl_merge", "k_isl_flatten", "k_isl_scan", "k_isl_roots", "k_isl_stats", "k_isl_mark", "k_isl_compact", "k_isl_remove",
                            "k_smooth_eval", "k_smooth_commit", "k_smooth_results",
                            "k_walk_stand", "k_walk_seed", "k_walk_relax", "k_walk_finish",
-                           "k_scatter_count", "k_scatter_scan", "k_scatter_write")
+                           "k_scatter_count", "k_scatter_scan", "k_scatter_write",
+                           "k_rec_mark", "k_rec_scan", "k_rec_list", "k_rec_capture", "k_rec_diff", "k_rec_pack", "k_rec_swap")
                if not any(k in name and "ScratchSize" in v for name, v in table.items())]
     if missing:
         os.remove(out)
@@ -115,7 +116,7 @@ def kernel_resources(remarks):
 def build_hip_casedump(force=False):
     """Test build of the HIP library that also records the case codes it looks up (tests/test_case_codes.py)."""
     out = os.path.join(CSRC, "libvoxels_hip_casedump.so")
-    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_walk.inl", "tv_walk.h", "vx_lod.inl", "tv_lod.h", "vx_scatter.inl", "tv_scatter.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
+    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_walk.inl", "tv_walk.h", "vx_undo.inl", "tv_undo.h", "vx_lod.inl", "tv_lod.h", "vx_scatter.inl", "tv_scatter.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
     if not force and not _newer(out, srcs):
         return out
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -127,7 +128,7 @@ def build_hip_conservative(force=False):
     """Test build of the HIP library whose in-kernel dependency flags use release / acquire fences instead of write-through
     stores and loads (-DVX_CONSERVATIVE_SYNC, vx_hip.hip): tests/test_gpu_parity.py compares it with the product library."""
     out = os.path.join(CSRC, "libvoxels_hip_conservative.so")
-    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_walk.inl", "tv_walk.h", "vx_lod.inl", "tv_lod.h", "vx_scatter.inl", "tv_scatter.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
+    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_walk.inl", "tv_walk.h", "vx_undo.inl", "tv_undo.h", "vx_lod.inl", "tv_lod.h", "vx_scatter.inl", "tv_scatter.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
     if not force and not _newer(out, srcs):
         return out
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -255,6 +256,19 @@ def build_walk_host(force=False):
     if not force and not _newer(out, srcs):
         return out
     subprocess.check_call(["g++", "-std=c++14", "-O2", "-fPIC", "-shared", "-o", out, os.path.join(d, "walk_host.cpp")], cwd=d)
+    return out
+
+
+def build_undo_host(force=False):
+    """Host side of the tests of the undo records: the kernels' pipeline of csrc/tv_undo.h run sequentially (mark, scan, list,
+    capture, diff, pack, swap), the entry checks and the layout of the header's structs - tests only (tests/test_undo.py,
+    tests/test_abi_undo.py)."""
+    d = os.path.join(ROOT, "tests", "undo")
+    out = os.path.join(d, "libvoxels_undo_host.so")
+    srcs = [os.path.join(d, "undo_host.cpp"), os.path.join(CSRC, "tv_undo.h"), os.path.join(ROOT, "include", "voxels_hip.h")]
+    if not force and not _newer(out, srcs):
+        return out
+    subprocess.check_call(["g++", "-std=c++14", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-o", out, os.path.join(d, "undo_host.cpp")], cwd=d)
     return out
 
 

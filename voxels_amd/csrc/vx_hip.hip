@@ -4280,6 +4280,7 @@ struct Backend {
 } // namespace
 
 #include "vx_host.inl"
+#include "vx_undo.inl"
 #include "vx_brush.inl"
 #include "vx_island.inl"
 #include "vx_smooth.inl"

@@ -179,6 +179,9 @@ struct vx_ctx {
 	// walk fields (vx_walk.inl): its device buffers
 	void* walkState = nullptr;
 	void (*walkFree)(vx_ctx*) = nullptr;
+	// undo records (vx_undo.inl): the records the context owns and its device buffers
+	void* undoState = nullptr;
+	void (*undoFree)(vx_ctx*) = nullptr;
 };
 
 // What only a backend with a device clock and a header the host can wait on offers (VX_BACKEND_HEADER_WAIT, defined by the
@@ -906,6 +909,7 @@ void vx_ctx_destroy(vx_ctx* c)
 	if (c->smoothFree) c->smoothFree(c);
 	if (c->scatterFree) c->scatterFree(c);
 	if (c->walkFree) c->walkFree(c);
+	if (c->undoFree) c->undoFree(c);
 	c->be.shutdown();
 	delete c;
 }
