@@ -859,6 +859,63 @@ int vx_scatter(vx_ctx*, uint32_t level, const vx_scatter_params* params, uint32_
  * (0, VX_SCATTER_MAX_DENSITY], a NaN in any float field, min_up > max_up, box_min > box_max on an axis, texture_slot > 7,
  * reserved != 0, and (device form) misaligned arrays.  A level with an empty table is VX_OK with zero counts (written). */
 
+/* ---- overlap queries: a level's triangles that meet query boxes --------------------------------------------------------------
+ * Which triangles are near this body: what a physics engine asks its triangle-mesh collider before narrow phase (Bullet's
+ * processAllTriangles(aabbMin, aabbMax), the custom mesh shapes of PhysX and Jolt), and also "is this spot free" (count only),
+ * "the surface under this decal", "the meshes of this region".  No reference counterpart: doc_source/Rendering.md leaves
+ * collision to the application.
+ *   scope      the REGULAR triangles of one level, as the last run on this context left them (the blocks of
+ *              vx_device_block_table(level)): the scope and staleness of the ray casts.  Transition meshes are not queried.
+ *              Mesh space: Y-up, voxels.  The calls read the level's ray-cast index (vx_raycast_prepare) and build it on
+ *              demand, as the sphere casts do.
+ *   box        closed, [lo, hi] per axis; lo == hi is allowed (a plane, a line, a point), and so is +-INF.  A NaN in lo or hi,
+ *              or lo[a] > hi[a] on any axis, makes an EMPTY query: count 0, not an error (the device form cannot validate
+ *              device arrays).  The reserved words are ignored.
+ *   match      triangle t of an entry, vertices v0, v1, v2 in index order, matches the box when on every axis a
+ *              min(v0[a], v1[a], v2[a]) <= hi[a] and max(v0[a], v1[a], v2[a]) >= lo[a]: float32 comparisons of the stored
+ *              positions and nothing else.  This is the triangle's bounding box against the query box, what the engines'
+ *              callbacks deliver; regular triangles lie within one cell of their level, so the bounding box is never looser
+ *              than a cell.  A separating-axis refinement is out of scope.
+ *   result     one vx_overlap_tri per match: the query's index, the entry of vx_device_block_table(level), that entry's id,
+ *              and the triangle's ordinal in the block's regular mesh (its indices 3*tri .. 3*tri+2).
+ *   corners    with a non-null corners array, triangle k of the result also gets 48 bytes at corners + 12 k floats:
+ *              v0.xyz, 0.0f, v1.xyz, 0.0f, v2.xyz, 0.0f - the position bytes of the vertex pool, so that a narrow phase needs
+ *              no second gather.
+ *   order      matches by query index, then by the block's coord_id ascending, then by tri ascending; no atomic decides
+ *              order.  By coord_id and not by entry: after incremental runs the table's order is no function of position,
+ *              and the result is the same list, up to entry and block_id, whether the surface came from a full run or from a
+ *              chain of incremental ones (as vx_scatter promises of its points).  ranges[q] = {matches before query q,
+ *              matches of query q} for every query.  Arrays are filled up to `capacity`; ranges and counts are always
+ *              complete.  If the total exceeds UINT32_MAX, no match, corner or range is written.
+ *   counts     triangles = what unlimited capacity would hold; pairs = the (query, entry) pairs with at least one match;
+ *              hit_queries = the queries with at least one match; max_per_query = the largest ranges[q].count.  All are
+ *              functions of the result set, none a count of work done.
+ *   stale      tables, offsets and meshes are those of the last run (vx_device_block_table).
+ * capacity == 0 with null output arrays is the count-only form.  The per-query scratch (16 bytes per query) is kept with the
+ * context and only ever grown; calls on one context must be ordered on one stream, as for the LOD selection. */
+#define VX_OVERLAP_MAX_QUERIES (1u << 20)
+typedef struct vx_overlap_box { float lo[3]; uint32_t reserved0; float hi[3]; uint32_t reserved1; } vx_overlap_box;   /* 32 bytes */
+typedef struct vx_overlap_tri { uint32_t query, entry, block_id, tri; } vx_overlap_tri;                               /* 16 bytes */
+typedef struct vx_overlap_range { uint32_t first, count; } vx_overlap_range;                                          /* per query */
+typedef struct vx_overlap_counts {      /* 32 bytes */
+	uint64_t triangles;         /* what unlimited capacity would hold */
+	uint64_t pairs;             /* (query, entry) pairs with at least one match */
+	uint32_t queries, hit_queries, max_per_query, reserved;
+} vx_overlap_counts;
+/* Device arrays (16-byte aligned; d_ranges: 8), enqueued on the context's stream (vx_set_stream), returns without waiting.
+ * With a current index: three launches, no copy, no synchronisation, and no allocation once the per-query scratch fits. */
+int vx_overlap_boxes_device(vx_ctx*, uint32_t level, const vx_overlap_box* d_boxes, uint32_t n, uint32_t capacity,
+                            vx_overlap_tri* d_tris, float* d_corners /* may be NULL */,
+                            vx_overlap_range* d_ranges /* may be NULL */, vx_overlap_counts* d_counts);
+/* Host arrays, synchronous.  VX_ERR_OVERFLOW when triangles > capacity, after writing the counts, the ranges and the first
+ * `capacity` results (and their corners). */
+int vx_overlap_boxes(vx_ctx*, uint32_t level, const vx_overlap_box* boxes, uint32_t n, uint32_t capacity,
+                     vx_overlap_tri* tris, float* corners, vx_overlap_range* ranges, vx_overlap_counts* counts);
+/* Both: VX_ERR_INVALID, before anything is launched, for a context without a surface, a level at or beyond what the last run
+ * produced, null counts, null boxes with n > 0, n > VX_OVERLAP_MAX_QUERIES, a null tris with a non-zero capacity, non-null
+ * corners with null tris, and (device form) misaligned arrays.  n == 0 is VX_OK with zero counts written; so is a level with
+ * an empty table, with zero ranges as well. */
+
 /* stats[0..3] = BlocksCalculated, TrivialCells, NonTrivialCells, DegenerateTrianglesRemoved; stats[4..19] =
  * PerCaseCellsCount (include/Polygonizer.h:110-132) */
 int vx_stats(vx_ctx* ctx, uint32_t stats[20]);

@@ -5,14 +5,16 @@ include/voxels_hip.h).  This package is the thin Python host side used by tests 
 the reference's operator interface for the path (Grid -> Polygonizer.Execute -> PolygonSurface levels/blocks)
 and fails loudly when the HIP library is missing — there is no CPU fallback.
 """
-from .binding import (BLOCK_INFO_DTYPE, BOX_DTYPE, DRAW_INDEXED_DTYPE, HIT_DTYPE, LOD_COUNTS_DTYPE, LOD_DRAW_DTYPE, POINT_HIT_DTYPE,
+from .binding import (BLOCK_INFO_DTYPE, BOX_DTYPE, DRAW_INDEXED_DTYPE, HIT_DTYPE, LOD_COUNTS_DTYPE, LOD_DRAW_DTYPE, OVERLAP_BOX_DTYPE, OVERLAP_COUNTS_DTYPE,
+                      OVERLAP_MAX_QUERIES, OVERLAP_RANGE_DTYPE, OVERLAP_TRI_DTYPE, POINT_HIT_DTYPE,
                       POINT_QUERY_DTYPE, RAY_DTYPE, RECORD_INFO_DTYPE, RECORD_MAX_BLOCKS, RECORD_MAX_BOXES, SCATTER_COUNTS_DTYPE, SCATTER_PARAMS_DTYPE, SCATTER_POINT_DTYPE,
                       SCATTER_RANGE_DTYPE, SPHERE_CAST_DTYPE, SPHERE_HIT_DTYPE, SWAP_RESULT_DTYPE, VERTEX_DTYPE, WALK_COUNTS_DTYPE,
                       WALK_GOAL_DTYPE, WALK_MAX_GOALS, WALK_QUERY_DTYPE, WALK_UNREACHED, HipLibrary, Level, Polygonizer, Record, VoxelsHipError,
-                      brush_boxes, hip_library_path, lod_params, lod_ranges, scatter_params, walk_query)
+                      brush_boxes, hip_library_path, lod_params, lod_ranges, overlap_boxes, scatter_params, walk_query)
 
 __all__ = ["BLOCK_INFO_DTYPE", "BOX_DTYPE", "DRAW_INDEXED_DTYPE", "HIT_DTYPE", "LOD_COUNTS_DTYPE", "LOD_DRAW_DTYPE", "POINT_HIT_DTYPE", "POINT_QUERY_DTYPE",
            "RAY_DTYPE", "SCATTER_COUNTS_DTYPE", "SCATTER_PARAMS_DTYPE", "SCATTER_POINT_DTYPE", "SCATTER_RANGE_DTYPE", "SPHERE_CAST_DTYPE", "SPHERE_HIT_DTYPE", "VERTEX_DTYPE",
            "WALK_COUNTS_DTYPE", "WALK_GOAL_DTYPE", "WALK_MAX_GOALS", "WALK_QUERY_DTYPE", "WALK_UNREACHED",
            "RECORD_INFO_DTYPE", "RECORD_MAX_BLOCKS", "RECORD_MAX_BOXES", "SWAP_RESULT_DTYPE", "Record", "brush_boxes",
-           "HipLibrary", "Level", "Polygonizer", "VoxelsHipError", "hip_library_path", "lod_params", "lod_ranges", "scatter_params", "walk_query"]
+           "HipLibrary", "Level", "Polygonizer", "VoxelsHipError", "hip_library_path", "lod_params", "lod_ranges", "scatter_params", "walk_query",
+           "OVERLAP_BOX_DTYPE", "OVERLAP_TRI_DTYPE", "OVERLAP_RANGE_DTYPE", "OVERLAP_COUNTS_DTYPE", "OVERLAP_MAX_QUERIES", "overlap_boxes"]

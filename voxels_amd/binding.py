@@ -132,6 +132,25 @@ def scatter_params(seed=0, density=1.0, min_up=-1.0, max_up=1.0, box_min=None, b
     return prm
 
 
+# vx_overlap_* (include/voxels_hip.h, overlap queries)
+OVERLAP_BOX_DTYPE = np.dtype([("lo", "<f4", 3), ("reserved0", "<u4"), ("hi", "<f4", 3), ("reserved1", "<u4")])
+OVERLAP_TRI_DTYPE = np.dtype([("query", "<u4"), ("entry", "<u4"), ("block_id", "<u4"), ("tri", "<u4")])
+OVERLAP_RANGE_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4")])
+OVERLAP_COUNTS_DTYPE = np.dtype([("triangles", "<u8"), ("pairs", "<u8"), ("queries", "<u4"), ("hit_queries", "<u4"),
+                                 ("max_per_query", "<u4"), ("reserved", "<u4")])
+assert OVERLAP_BOX_DTYPE.itemsize == 32 and OVERLAP_TRI_DTYPE.itemsize == 16
+assert OVERLAP_RANGE_DTYPE.itemsize == 8 and OVERLAP_COUNTS_DTYPE.itemsize == 32
+OVERLAP_MAX_QUERIES = 1 << 20
+
+
+def overlap_boxes(lo, hi):
+    """an OVERLAP_BOX_DTYPE array from corners lo, hi of shape [n, 3] (or [3]: one box): closed boxes, mesh space (Y-up, voxels)"""
+    lo, hi = np.asarray(lo, np.float32).reshape(-1, 3), np.asarray(hi, np.float32).reshape(-1, 3)
+    boxes = np.zeros(max(len(lo), len(hi)), OVERLAP_BOX_DTYPE)
+    boxes["lo"], boxes["hi"] = lo, hi
+    return boxes
+
+
 class VoxelsHipError(RuntimeError):
     pass
 
@@ -321,6 +340,11 @@ class HipLibrary:
         if self.has_scatter:
             lib.vx_scatter_device.argtypes = [vp, u32, vp, u32, vp, vp, vp]
             lib.vx_scatter.argtypes = [vp, u32, vp, u32, vp, vp, vp]
+        # overlap queries: HIP builds only, likewise
+        self.has_overlap = hasattr(lib, "vx_overlap_boxes")
+        if self.has_overlap:
+            lib.vx_overlap_boxes_device.argtypes = [vp, u32, vp, u32, u32, vp, vp, vp, vp]
+            lib.vx_overlap_boxes.argtypes = [vp, u32, vp, u32, u32, vp, vp, vp, vp]
         self.lib = lib
         self.path = path
         self.backend = lib.vx_backend().decode()
@@ -1047,6 +1071,54 @@ class Polygonizer:
         prm = np.ascontiguousarray(params, SCATTER_PARAMS_DTYPE)
         self._check(self._scatter_lib().vx_scatter_device(self._h, int(level), _ptr(prm), int(capacity), C.c_void_p(d_points),
                                                           C.c_void_p(d_ranges), C.c_void_p(d_counts)), "vx_scatter_device")
+
+    def _overlap_lib(self):
+        if not self._L.has_overlap:
+            raise VoxelsHipError("%s has no overlap queries (vx_overlap_boxes*)" % self._L.path)
+        return self._L.lib
+
+    def overlap_boxes_raw(self, level, boxes, capacity, corners=False):
+        """one vx_overlap_boxes call: (return code, tris OVERLAP_TRI_DTYPE[capacity], corners float32 [capacity, 3, 4] or None,
+        ranges OVERLAP_RANGE_DTYPE per query, counts record); capacity 0 is the count-only form"""
+        lib = self._overlap_lib()
+        boxes = np.ascontiguousarray(boxes, OVERLAP_BOX_DTYPE).reshape(-1)
+        cap = int(capacity)
+        tris, counts = np.zeros(cap, OVERLAP_TRI_DTYPE), np.zeros(1, OVERLAP_COUNTS_DTYPE)
+        crn = np.zeros((cap, 3, 4), np.float32) if corners and cap else None
+        ranges = np.zeros(boxes.size, OVERLAP_RANGE_DTYPE)
+        rc = lib.vx_overlap_boxes(self._h, int(level), _ptr(boxes) if boxes.size else None, boxes.size, cap, _ptr(tris) if cap else None,
+                                  None if crn is None else _ptr(crn), _ptr(ranges) if boxes.size else None, _ptr(counts))
+        return rc, tris, crn, ranges, counts[0]
+
+    def overlap_boxes(self, level, boxes, capacity=None, corners=False):
+        """vx_overlap_boxes: the regular triangles of a level whose bounding boxes meet each of the closed query boxes
+        (overlap_boxes(lo, hi)), ordered by query, coord_id, tri: (tris OVERLAP_TRI_DTYPE, corners float32 [k, 3, 4] or None,
+        ranges OVERLAP_RANGE_DTYPE per query, counts dict).  capacity None: two calls, the counts first, then the fill; with
+        a capacity, at most that many results come back (counts["triangles"] says how many there are)."""
+        cap = capacity
+        if cap is None:
+            rc, _, _, _, counts = self.overlap_boxes_raw(level, boxes, 0)
+            if rc != -3:
+                self._check(rc, "vx_overlap_boxes")
+            if int(counts["triangles"]) > 0xFFFFFFFF:
+                raise VoxelsHipError("vx_overlap_boxes: %d results do not fit a 32-bit capacity" % int(counts["triangles"]))
+            cap = int(counts["triangles"])
+        rc, tris, crn, ranges, counts = self.overlap_boxes_raw(level, boxes, cap, corners)
+        if rc != -3 or capacity is None:
+            self._check(rc, "vx_overlap_boxes")
+        c = {k: int(counts[k]) for k in OVERLAP_COUNTS_DTYPE.names}
+        filled = min(c["triangles"], cap)
+        if corners and crn is None:
+            crn = np.zeros((0, 3, 4), np.float32)
+        return tris[:filled], None if crn is None else crn[:filled], ranges, c
+
+    def overlap_boxes_device(self, level, d_boxes, n, capacity, d_tris, d_corners, d_ranges, d_counts):
+        """vx_overlap_boxes_device: n OVERLAP_BOX_DTYPE boxes at device address d_boxes, arrays at device addresses (ints, 16-byte
+        aligned, d_ranges 8; d_corners and d_ranges may be None, d_tris with capacity 0); queued on the context's stream
+        (set_stream), returns without waiting."""
+        self._check(self._overlap_lib().vx_overlap_boxes_device(self._h, int(level), C.c_void_p(d_boxes), int(n), int(capacity),
+                                                                C.c_void_p(d_tris), C.c_void_p(d_corners), C.c_void_p(d_ranges),
+                                                                C.c_void_p(d_counts)), "vx_overlap_boxes_device")
 
     def stats(self):
         out = np.zeros(20, np.uint32)

@@ -4289,3 +4289,4 @@ struct Backend {
 #include "vx_shape.inl"
 #include "vx_lod.inl"
 #include "vx_scatter.inl"
+#include "vx_overlap.inl"

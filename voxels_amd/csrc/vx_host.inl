@@ -182,6 +182,9 @@ struct vx_ctx {
 	// undo records (vx_undo.inl): the records the context owns and its device buffers
 	void* undoState = nullptr;
 	void (*undoFree)(vx_ctx*) = nullptr;
+	// overlap queries (vx_overlap.inl): its device buffers
+	void* overlapState = nullptr;
+	void (*overlapFree)(vx_ctx*) = nullptr;
 };
 
 // What only a backend with a device clock and a header the host can wait on offers (VX_BACKEND_HEADER_WAIT, defined by the
@@ -910,6 +913,7 @@ void vx_ctx_destroy(vx_ctx* c)
 	if (c->scatterFree) c->scatterFree(c);
 	if (c->walkFree) c->walkFree(c);
 	if (c->undoFree) c->undoFree(c);
+	if (c->overlapFree) c->overlapFree(c);
 	c->be.shutdown();
 	delete c;
 }
