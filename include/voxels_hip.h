@@ -52,7 +52,8 @@ typedef struct vx_block_info {
 typedef struct vx_exec_info {
 	uint32_t levels;            /* LOD levels produced (PolygonSurface::GetLevelsCount) */
 	uint32_t retries;           /* re-runs after growing the output pools */
-	float device_ms;            /* device time of the last run, always > 0.  A full run on the single-stream path (three launches;
+	float device_ms;            /* device time of the last run, always > 0.  A full run on the single-stream path (three launches,
+	                             * or two while the slot plan is kept - then the first kernel is k_main, vx_slot_plan_counts;
 	                             * stage timing off): the device's constant 100 MHz clock, from the moment the first workgroup of
 	                             * the first kernel starts to the publication of the run's header by the last kernel - a few
 	                             * microseconds less than the interval between two HIP events around the same launches, which also
@@ -932,6 +933,15 @@ int vx_transition_path_counts(vx_ctx* ctx, uint32_t out[2]);
  * range).  VX_MATSTORE=0 (read at context creation) keeps no store: every run votes.  Diagnostics: caches, meshes and
  * statistics are the same either way. */
 int vx_material_path_counts(vx_ctx* ctx, uint32_t out[2]);
+
+/* Full runs of this context (every attempt of vx_polygonize / vx_polygonize_from, since the context was created) by where their
+ * slots came from: out[0] = handed out by the run itself (k_run_head, or the classification pass of the chain of launches),
+ * out[1] = kept - a full single-stream run that read the cell map has handed them out, nothing they depend on has changed
+ * since (BF_Empty flags, distances through the sign summaries and the cell counts, the context's range, the level count) and
+ * nobody has handed out slots in between (incremental and partial runs do): the run launches no k_run_head, and its
+ * device_ms starts with k_main.  VX_PLAN=0 (read at context creation) keeps no plan: every run hands out its slots.
+ * Diagnostics: tables, meshes, statistics and vx_exec_info are the same either way.  HIP builds only. */
+int vx_slot_plan_counts(vx_ctx* ctx, uint64_t out[2]);
 
 /* The device forms of the exactness-critical arithmetic checked exhaustively on the GPU they run on (the reference does
  * this arithmetic on the host: t = (v1 << 8) / (v1 - v0), src/TransVoxelImpl.cpp:1591; normalizeFixZero, :93-103):

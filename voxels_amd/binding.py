@@ -275,6 +275,10 @@ class HipLibrary:
         self.has_material_path_counts = hasattr(lib, "vx_material_path_counts")
         if self.has_material_path_counts:
             lib.vx_material_path_counts.argtypes = [vp, vp]
+        # (the slot plan: HIP builds only, and absent from builds made before it)
+        self.has_slot_plan = hasattr(lib, "vx_slot_plan_counts")
+        if self.has_slot_plan:
+            lib.vx_slot_plan_counts.argtypes = [vp, vp]
         lib.vx_selftest.argtypes = [vp, vp]
         lib.vx_stage_layout.argtypes = [vp, C.POINTER(C.c_int)]
         lib.vx_set_stage_timing.argtypes = [vp, C.c_int]
@@ -1137,4 +1141,12 @@ class Polygonizer:
             raise VoxelsHipError("this library has no vx_material_path_counts")
         out = np.zeros(2, np.uint32)
         self._check(self._lib.vx_material_path_counts(self._h, _ptr(out)), "vx_material_path_counts")
+        return int(out[0]), int(out[1])
+
+    def slot_plan_counts(self):
+        """vx_slot_plan_counts: (handed out, kept) - the full runs of this context by where their slots came from, cumulative."""
+        if not self._L.has_slot_plan:
+            raise VoxelsHipError("this library has no vx_slot_plan_counts")
+        out = np.zeros(2, np.uint64)
+        self._check(self._lib.vx_slot_plan_counts(self._h, _ptr(out)), "vx_slot_plan_counts")
         return int(out[0]), int(out[1])

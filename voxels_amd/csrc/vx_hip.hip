@@ -1,6 +1,7 @@
 // vx_hip.hip — gfx950 (MI355X / CDNA4) kernels and HIP backend of libvoxels_hip.so.
 //
-// A full run of a terrain-like grid is THREE launches on one stream:
+// A full run of a terrain-like grid is THREE launches on one stream - and TWO, k_main | k_tail, while the grid
+// has not changed since a run handed out the slots (the slot plan, vx_host.inl: k_run_head's whole output is still in memory):
 //   k_run_head    what the BF_Empty flags and the sign summaries say about a block; the blocks that are not quiet get their
 //                 level-0 slots and their ancestors the slots of the levels above (workgroup = an aligned 8 x 8 x 4 box)
 //   k_main        (vx_main.inl) every block of every level: two queues handed out to persistent workgroups - the level-0
@@ -56,6 +57,7 @@
 #define VX_BACKEND_CELL_MAP 1    // this backend keeps the cell map (MirrorState::cellMap; vx_host.inl ensure_cell_map, vx_grid_cell_map)
 #define VX_BACKEND_MAT_STORE 1   // this backend keeps the material store (MatStoreLevel; vx_host.inl ensure_mat_store, k_main's copy items)
 #define VX_BACKEND_HEADER_WAIT 1 // this backend times a run by the device clock and lets the host wait for the header (vx_host.inl RunClock)
+#define VX_BACKEND_SLOT_PLAN 1   // this backend keeps k_run_head's output across full runs of an unchanged grid (vx_host.inl slot plan, k_tail's seeds)
 
 namespace {
 using namespace tv;
@@ -2811,12 +2813,27 @@ __global__ __launch_bounds__(LIST_WG) void k_list_write(ExecParamsDev p, ListPla
 // device-wide first (records and list counts are read by list workgroups on other XCDs: through write-through loads where
 // the list pass reads what this launch wrote).
 // ------------------------------------------------------------------------------------------------------
+// The start state of a run that launches no k_run_head (the slot plan, vx_host.inl): every counter 0 - except the words the head
+// would have added into, which are taken from the current header, where they are final since this run's head (or were seeded
+// by the tail of the run before): the slot counts of the run's levels and the head's two statistics.
+struct SeedRanges {
+	u32* header;
+	u32 headerWords;
+	u32* listCounts;
+	u32 listWgs;
+	const u32* from;  // the current header
+	u32 levels;       // words [0, levels): the slot counts
+	u32 words[2];     // the head's statistics: "blocks read" (largeBlocks + 1), "blocks calculated" on level 0 (stats + 2)
+};
+
 struct TailPlan {
 	u32 wgs0, wgs1, listWgs; // workgroups: general pass of level 0 | of the levels >= 1 | lists
 	u32 levels;
 	u32* slowDone;           // finished general workgroups (a header word: zeroed with the run's counters)
 	u32* roleTicket;         // (the header word behind it) roles handed out in order of arrival, see below
 	ResetRanges next;        // the counters and maps of the OTHER set, which the next run will use: put into their start state here
+	                         // (header == nullptr: nothing - a run that keeps the slot plan leaves the clean set as it found it)
+	SeedRanges seed;         // the counters a run that keeps this run's slots will use (header == nullptr: none)
 };
 
 // Roles.  Nothing was handed on (the rule on a terrain; two header words say so): the general workgroups find nothing, the list
@@ -2865,6 +2882,16 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(3))) void k_
 		for (u32 i = (role - general) * WG + threadIdx.x; i * 4u < t.next.start[MAX_LEVELS] || i < t.next.listWgs; i += lanes) {
 			reset_words(t.next, i);
 			if (i < t.next.listWgs) t.next.listCounts[i] = 0;
+		}
+	}
+	if (t.seed.header) {
+		const u32 lanes = t.listWgs * WG;
+		for (u32 i = (role - general) * WG + threadIdx.x; i < t.seed.headerWords || i < t.seed.listWgs; i += lanes) {
+			if (i < t.seed.headerWords) {
+				const bool kept = i < t.seed.levels || i == t.seed.words[0] || i == t.seed.words[1];
+				t.seed.header[i] = kept ? TV_LOAD_THROUGH(t.seed.from + i) : 0u;
+			}
+			if (i < t.seed.listWgs) t.seed.listCounts[i] = 0;
 		}
 	}
 }
@@ -3310,7 +3337,7 @@ struct Backend {
 	int device = 0;
 	bool ok = true;
 	// launch geometry knobs, read from the environment once when the context is created (tuning aids)
-	// Runtime knobs (read once per context).  Ten in all with VX_POOL_SLACK and VX_HOST_TIMING (vx_host.inl); each selects a path
+	// Runtime knobs (read once per context).  Eleven in all with VX_POOL_SLACK and VX_HOST_TIMING (vx_host.inl); each selects a path
 	// that production runs reach through their data - dense surfaces, grids beyond 1024^3, blocks with zero samples - so that the
 	// tests can drive those paths on small fixtures (tests/test_gpu_parity.py::test_hip_runtime_knobs_select_equivalent_paths).
 	struct Tuning {
@@ -3323,6 +3350,7 @@ struct Backend {
 		u32 syncWait = 0;    // VX_SYNC_WAIT=1: a full run is waited for with hipStreamSynchronize where the default waits for its header (wait_published)
 		u32 cellMap = 1;     // VX_CELLMAP=0: no cell map - the level-0 blocks of a single-stream run form their own bitmaps, its level-1 material blocks their children's
 		u32 matStore = 1;    // VX_MATSTORE=0: no material store - every full run votes the material caches of the levels >= 1
+		u32 plan = 1;        // VX_PLAN=0: no slot plan - every full run launches k_run_head
 		// fixed since round 6 (were environment variables while they were being measured; profiles/HISTORY.md has the sweeps)
 		static constexpr u32 classifyRowGroup = 4, regWgsPerCu = 20, f1WgsPerCu = 20, foldBlocks = 65536, upWgsPerCu = 5, mainWgsPerCu = 4, mainBatch = 2, mainUpperNum = 1, mainUpperDen = 4;
 		bool fast0() const { return (fast & 1u) != 0; }
@@ -3358,6 +3386,7 @@ struct Backend {
 		tune.syncWait = env_u32("VX_SYNC_WAIT", 0);
 		tune.cellMap = env_u32("VX_CELLMAP", 1);
 		tune.matStore = env_u32("VX_MATSTORE", 1);
+		tune.plan = env_u32("VX_PLAN", 1);
 		hipDeviceProp_t prop;
 		if (hipGetDeviceProperties(&prop, device) == hipSuccess) cus = prop.multiProcessorCount;
 		if (!check(hipStreamCreateWithFlags(&ownStream, hipStreamNonBlocking), "hipStreamCreate")) { err = lastError; return false; }
@@ -3673,6 +3702,7 @@ struct Backend {
 	bool pendingClean = false;   // the run's counters and the maps of the levels >= 1 are in their start state already (k_tail of the run before)
 	ResetRanges nextReset = {};  // what k_tail puts into its start state for the next run (header == nullptr: nothing)
 	bool tailCleaned = false;    // the last k_tail did
+	bool tailSeeded = false;     // ... and seeded the counters of a run that keeps the slots (nextSeed)
 	void set_next_reset(u32* header, u32 headerWords, u32* listCounts, u32 listWgs, int* const* maps, const u32* ids)
 	{
 		ResetRanges r;
@@ -3685,6 +3715,18 @@ struct Backend {
 		r.start[MAX_LEVELS] = run;
 		nextReset = r;
 	}
+	// The slot plan (vx_host.inl): what k_tail seeds for a run that will launch no head (header == nullptr: nothing) ...
+	SeedRanges nextSeed = {};
+	void set_next_seed(u32* header, u32 headerWords, u32* listCounts, u32 listWgs, const u32* from, u32 levels, u32 wordRead, u32 wordCalculated)
+	{
+		SeedRanges r;
+		r.header = header; r.headerWords = headerWords; r.listCounts = listCounts; r.listWgs = listWgs;
+		r.from = from; r.levels = levels; r.words[0] = wordRead; r.words[1] = wordCalculated;
+		nextSeed = r;
+	}
+	// ... and whether this run is such a run: its counters were seeded, its slots are in place - no k_reset, no k_run_head, and
+	// workgroup 0 of k_main leaves the clock (set per attempt by the host, cleared by the launch it applies to)
+	bool keepSlots = false;
 	u32 headWorkgroups = 0; // of the last k_run_head launch: that many block-class partial sums sit behind the header
 	template <typename P>
 	void run_reset(const P& p, u32 levels, u32* header, u32 headerWords, u32* listCounts, u32 listWgs, bool alreadyClean = false)
@@ -3739,6 +3781,11 @@ struct Backend {
 			// no classification pass: k_run_head hands out the slots, k_main's level-0 blocks form their own bitmaps
 			ResetRanges r = pendingReset;
 			pendingReset.header = nullptr;
+			if (keepSlots) { // (the slot plan: the head's output of an earlier run is in place)
+				headWorkgroups = 0;
+				stage_mark(1);
+				return;
+			}
 			if (r.header && !pendingClean) {
 				const u32 lanes = std::max<u32>((r.start[MAX_LEVELS] + 3) / 4, r.listWgs);
 				hipLaunchKernelGGL(k_reset, dim3((lanes + WG - 1) / WG), dim3(WG), 0, stream, dev(p), r);
@@ -3971,13 +4018,15 @@ struct Backend {
 		if (emitFrom && withLevel0) {
 			// (no level-0 queue: the persistent workgroups are the upper queue's)
 			plan.level0 = 0u; plan.upperNum = plan.upperDen = 1u; plan.emitFrom = emitFrom;
-			launch_with_event(k_main<false, true>, dim3(grid), UP_TAB_LDS + MAIN_STATE_LDS, dev(p), plan);
+			launch_with_event(k_main<false, true>, dim3(grid), UP_TAB_LDS + MAIN_STATE_LDS, dev(p), plan, (u32*)nullptr);
 		} else if (withLevel0 && p.G.cellMap) {
 			plan.matMode = p.G.matStore[1].index ? matMode : 0u;
 			matModeUsed = plan.matMode;
-			launch_with_event(k_main<false, false, true>, dim3(grid), UP_TAB_LDS + MAIN_STATE_LDS, dev(p), plan);
+			// (a run that keeps its slots has no head: the run's clock starts here)
+			launch_with_event(k_main<false, false, true>, dim3(grid), UP_TAB_LDS + MAIN_STATE_LDS, dev(p), plan, keepSlots ? clockStart : (u32*)nullptr);
+			keepSlots = false;
 		} else
-			launch_with_event(k_main<false>, dim3(grid), UP_TAB_LDS + (withLevel0 ? MAIN_STATE_LDS : UP_STATE_LDS), dev(p), plan);
+			launch_with_event(k_main<false>, dim3(grid), UP_TAB_LDS + (withLevel0 ? MAIN_STATE_LDS : UP_STATE_LDS), dev(p), plan, (u32*)nullptr);
 		check(hipGetLastError(), "k_main launch");
 	}
 
@@ -4027,7 +4076,7 @@ struct Backend {
 			items += v * (1u + (l < plan.fastEnd ? 1u : 0u) + (p.levels[l].hasTransitions ? 1u : 0u));
 			if (l >= plan.fastEnd) upperVol += v;
 		}
-		hipLaunchKernelGGL(k_main<true>, dim3(std::max<u32>(1u, std::min<u32>(items, slots))), dim3(WG), UP_TAB_LDS + MAIN_STATE_LDS, stream, dev(p), plan);
+		hipLaunchKernelGGL(k_main<true>, dim3(std::max<u32>(1u, std::min<u32>(items, slots))), dim3(WG), UP_TAB_LDS + MAIN_STATE_LDS, stream, dev(p), plan, (u32*)nullptr);
 		check(hipGetLastError(), "k_main (incremental) launch");
 		if (large0Expected || largeUpperExpected) {
 			// (level 0 and the levels above it are announced apart: the coarse levels of a terrain hold such blocks where level 0
@@ -4240,15 +4289,17 @@ struct Backend {
 		publish = HeaderPublish();
 		const bool tail = tailPending;
 		tailPending = false;
-		tailCleaned = false;
+		tailCleaned = tailSeeded = false;
 		if (tail) {
 			// (with or without list workgroups: the general passes were left to this launch)
 			TailPlan t;
 			t.wgs0 = tailWgs[0]; t.wgs1 = tailWgs[1]; t.listWgs = wgs; t.levels = levels; t.slowDone = tailDone; t.roleTicket = tailDone + 1;
 			t.next = nextReset;
-			if (!wgs) t.next.header = nullptr;
+			t.seed = nextSeed;
+			if (!wgs) t.next.header = t.seed.header = nullptr;
 			tailCleaned = t.next.header != nullptr;
-			nextReset.header = nullptr;
+			tailSeeded = t.seed.header != nullptr;
+			nextReset.header = nextSeed.header = nullptr;
 			const u32 lds = std::max<u32>(R0_TAB_LDS + sizeof(Reg0State<REG_CAP_SMALL>), REG_TAB_LDS + sizeof(RegStateT<REG_CAP_SMALL>));
 			if (t.wgs0 + t.wgs1 + wgs) hipLaunchKernelGGL(k_tail, dim3(t.wgs0 + t.wgs1 + wgs), dim3(WG), lds, stream, dev(p), plan, wgs ? pub : HeaderPublish(), t);
 			check(hipGetLastError(), "k_tail launch");

@@ -47,7 +47,7 @@ typedef ListedBlock EmittedBlock;
 
 // largest grid edge: 2048 = 8 LOD levels (MAX_LEVELS) and 32-bit element offsets inside a block neighbourhood
 enum { VX_MAX_GRID = 2048 };
-enum { HDR_WORDS = 576, HDR_LISTS = 8, HDR_CURSORS = 32, HDR_STATS = 128, HDR_WORK = 160, HDR_LARGE = 176, HDR_SLOW = 224, HDR_UPPER = 256, HDR_GIVEUP = 288, HDR_PUBLISHED = 289 /* workgroups of the list pass that are done; in the host copy: the tag of the run whose header this is */, HDR_L0HEAD = 320 /* the head of k_main's level-0 queue, one for the chip */, HDR_CLOCK0 = 352, HDR_CLOCK1 = 384 /* the 100 MHz clock at the start of k_run_head / at the publication of the header */, HDR_PARTIALS = 32768 }; // counters spread over 128-byte lines
+enum { HDR_WORDS = 576, HDR_LISTS = 8, HDR_CURSORS = 32, HDR_STATS = 128, HDR_WORK = 160, HDR_LARGE = 176, HDR_SLOW = 224, HDR_UPPER = 256, HDR_GIVEUP = 288, HDR_PUBLISHED = 289 /* workgroups of the list pass that are done; in the host copy: the tag of the run whose header this is */, HDR_L0HEAD = 320 /* the head of k_main's level-0 queue, one for the chip */, HDR_CLOCK0 = 352, HDR_CLOCK1 = 384 /* the 100 MHz clock at the start of k_run_head (of k_main in a run that keeps the slot plan) / at the publication of the header */, HDR_PARTIALS = 32768 }; // counters spread over 128-byte lines
 
 } // namespace
 
@@ -90,11 +90,26 @@ struct vx_ctx {
 	// Two sets of what a full run needs in its start state - the header's counters, the block -> slot maps of the levels >= 1,
 	// the list counts: a run works on one set, and its last kernel (k_tail) resets the other for the run behind it, which then
 	// starts without k_reset.  dHeader / dListCounts / lv[L].slotOf, nActive, listCounts always name the current set.
-	void* headerSet[2] = { nullptr, nullptr };
-	void* listCountSet[2] = { nullptr, nullptr };
+	// Which set of counters and which set of maps are choices of their own (runSet, mapSet).  Without the slot plan both flip
+	// together between 0 and 1.  With it (below) there is a third set of counters, so that k_tail can leave one set in the start
+	// state of a run whose head hands out slots (cleanSet: all zero, and the other set of maps at -1) AND one in the start state
+	// of a run that keeps this run's slots (seedSet: zero but for the slot counts and the head's statistics; such a run stays
+	// on the maps that hold the plan).  -1: no such set.
+	void* headerSet[3] = { nullptr, nullptr, nullptr };
+	void* listCountSet[3] = { nullptr, nullptr, nullptr };
 	int* upperMaps[2][MAX_LEVELS] = {};
-	u32 runSet = 0;
-	bool otherSetClean = false;
+	u32 runSet = 0, mapSet = 0;
+	int cleanSet = -1, seedSet = -1;
+	// The slot plan (backends with VX_BACKEND_SLOT_PLAN): everything k_run_head writes - slotOf and slotCoord of every level, skip and
+	// ntCount of level 0, the slot counts, its two statistics - is a function of the BF_Empty flags, the sign summaries, the
+	// cell counts, the rank's block range and the run's level count alone.  valid = a full single-stream run that read the
+	// cell map has handed out the slots of planLevels levels, they are still in place (nobody has handed out or overwritten
+	// slots since) and nothing they depend on has changed (slot_plan_drop sits beside every mat_store_invalidate of a changed
+	// grid): full runs of planLevels levels then launch no k_run_head.  planRuns: full-run attempts of this context whose slots
+	// were handed out | kept (vx_slot_plan_counts).
+	bool planOn = false, planValid = false;
+	u32 planLevels = 0;
+	uint64_t planRuns[2] = { 0, 0 };
 	u32 listWgs = 0;
 	void* haloBuf[4] = { nullptr, nullptr, nullptr, nullptr }; // staging of the halo messages: send below, send above, receive from below, receive from above
 	size_t haloCap[4] = { 0, 0, 0, 0 };
@@ -240,6 +255,9 @@ u32 ref_levels(u32 n)
 }
 
 void mat_store_invalidate(vx_ctx* c) { c->matStoreValid = false; }
+void slot_plan_drop(vx_ctx* c) { c->planValid = false; }
+// something the material store and the slot plan depend on has changed (or is about to be freed)
+void kept_state_invalidate(vx_ctx* c) { mat_store_invalidate(c); slot_plan_drop(c); }
 
 void free_level_tables(vx_ctx* c)
 {
@@ -248,13 +266,13 @@ void free_level_tables(vx_ctx* c)
 	for (void* p : c->matStoreAllocs) c->be.free(p);
 	c->matStoreAllocs.clear();
 	memset(c->matStore, 0, sizeof(c->matStore));
-	mat_store_invalidate(c);
+	kept_state_invalidate(c);
 	c->tablesN = 0;
 }
 
 void release_grid(vx_ctx* c)
 {
-	mat_store_invalidate(c);
+	kept_state_invalidate(c);
 	if (c->ownsGrid || c->ownsSlab) {
 		c->be.free(c->dDist); c->be.free(c->dMat); c->be.free(c->dBlend); c->be.free(c->dFlags);
 	}
@@ -272,7 +290,7 @@ void free_bricks(vx_ctx* c)
 	c->be.free(c->dCellMap); c->dCellMap = nullptr;
 	c->be.free(c->dCellCount); c->dCellCount = nullptr;
 	c->cellMapStale = true;
-	mat_store_invalidate(c);
+	kept_state_invalidate(c);
 	c->brickN = 0;
 	c->bricksStale = true;
 }
@@ -346,7 +364,7 @@ bool ensure_bricks(vx_ctx* c)
 		c->be.run_rebrick(resident_view(c), dr, mr, mirror_state(c), box, nullptr, 0);
 		c->bricksStale = false;
 		c->cellMapStale = true;
-		mat_store_invalidate(c);
+		kept_state_invalidate(c);
 	}
 	return true;
 }
@@ -370,7 +388,7 @@ void ensure_cell_map(vx_ctx* c)
 // wait for a full copy anyway (the rows of a halo exchange are written into the mirrors by its unpack kernel)
 void rebrick_blocks(vx_ctx* c, const u32* dIds, u32 count)
 {
-	mat_store_invalidate(c); // (every device edit passes here: distances, materials or blends of the listed blocks have changed, and their flags)
+	kept_state_invalidate(c); // (every device edit passes here: distances, materials or blends of the listed blocks have changed, and their flags)
 	if (!c->be.wants_bricks() || c->bricksStale || !c->dBrick[0] || !count) return;
 	int dr[4], mr[4];
 	resident_ranges(c, dr, mr);
@@ -379,17 +397,18 @@ void rebrick_blocks(vx_ctx* c, const u32* dIds, u32 count)
 }
 
 
-// the set of counters, upper-level maps and list counts the next full run works on (vx_ctx::headerSet)
-void select_run_set(vx_ctx* c, u32 set)
+// the set of counters and list counts, and the set of upper-level maps, the next full run works on (vx_ctx::headerSet)
+void select_run_set(vx_ctx* c, u32 set, u32 maps)
 {
 	c->runSet = set;
+	c->mapSet = maps;
 	c->dHeader = c->headerSet[set];
 	c->dListCounts = c->listCountSet[set];
 	size_t at = 0;
 	for (u32 L = 0; L < c->refLevels && L < MAX_LEVELS; ++L) {
 		LevelDesc& d = c->lv[L];
 		d.nActive = (u32*)c->dHeader + L;
-		if (L) d.slotOf = c->upperMaps[set][L];
+		if (L) d.slotOf = c->upperMaps[maps][L];
 		d.listCounts = (u32*)c->dListCounts + at;
 		at += ((size_t)d.cnt * d.cnt * d.cnt + LIST_WG - 1) / LIST_WG;
 	}
@@ -493,7 +512,8 @@ bool ensure_level_tables(vx_ctx* c)
 		c->dListCounts = alloc(wgs * 4 + 16);
 		c->listCountSet[0] = c->dListCounts;
 		c->listCountSet[1] = alloc(wgs * 4 + 16);
-		if (!c->dListCounts || !c->listCountSet[1]) return false;
+		c->listCountSet[2] = c->headerSet[2] ? alloc(wgs * 4 + 16) : nullptr;
+		if (!c->dListCounts || !c->listCountSet[1] || (c->headerSet[2] && !c->listCountSet[2])) return false;
 		c->listWgs = (u32)wgs;
 		size_t at = 0; // every level's segment of the counts (the list kernel's workgroups are laid out the same way, ListPlan::wgStart)
 		for (u32 L = 0; L < c->refLevels && L < MAX_LEVELS; ++L) {
@@ -502,8 +522,8 @@ bool ensure_level_tables(vx_ctx* c)
 		}
 	}
 	c->tablesN = c->n; c->tablesZb0 = zb0; c->tablesZb1 = zb1; c->tablesYb0 = yb0; c->tablesYb1 = yb1;
-	c->otherSetClean = false;
-	select_run_set(c, 0);
+	c->cleanSet = c->seedSet = -1;
+	select_run_set(c, 0, 0);
 	return true;
 }
 
@@ -873,6 +893,12 @@ int vx_ctx_create(int device_index, vx_ctx** out)
 	c->dHeader = c->be.alloc((HDR_WORDS + HDR_PARTIALS) * 4); // header + the block-class partial sums of k_run_head (one word per workgroup)
 	c->headerSet[0] = c->dHeader;
 	c->headerSet[1] = c->be.alloc((HDR_WORDS + HDR_PARTIALS) * 4);
+#if defined(VX_BACKEND_SLOT_PLAN)
+	// VX_PLAN=0: no slot plan, two sets of counters - every full run launches k_run_head
+	c->planOn = c->be.tune.plan != 0;
+	if (c->planOn) c->headerSet[2] = c->be.alloc((HDR_WORDS + HDR_PARTIALS) * 4);
+	if (c->planOn && !c->headerSet[2]) { vx_ctx_destroy(c); return VX_ERR_DEVICE; }
+#endif
 	if (!c->dTables || !c->dLut || !c->dHeader || !c->headerSet[1] || !c->be.h2d(c->dTables, img.data(), TAB_FT_BYTES)) {
 		vx_ctx_destroy(c);
 		return VX_ERR_DEVICE;
@@ -895,7 +921,7 @@ void vx_ctx_destroy(vx_ctx* c)
 	free_level_tables(c);
 	c->be.free(c->dVerts); c->be.free(c->dIdx);
 	c->be.free(c->dVertsSpare); c->be.free(c->dIdxSpare); c->be.free(c->dSeg);
-	c->be.free(c->dTables); c->be.free(c->dLut); c->be.free(c->headerSet[0]); c->be.free(c->headerSet[1]);
+	c->be.free(c->dTables); c->be.free(c->dLut); c->be.free(c->headerSet[0]); c->be.free(c->headerSet[1]); c->be.free(c->headerSet[2]);
 	c->be.free(c->dDirty); c->be.free(c->dWork); c->be.free(c->dGather);
 	c->be.free_pinned(c->hRecs);
 	c->be.free(c->dDirtyTicket);
@@ -1266,7 +1292,7 @@ int vx_grid_invalidate(vx_ctx* c)
 	// the caller rewrote attached memory in place: the brick mirrors, lattice copies and sign summaries are rebuilt by the
 	// next polygonization, and whatever surface the context holds no longer describes the grid
 	c->bricksStale = true;
-	mat_store_invalidate(c);
+	kept_state_invalidate(c);
 	c->haveSurface = false;
 	return VX_OK;
 }
@@ -1398,7 +1424,7 @@ void refresh_halo_layers(vx_ctx* c)
 	const int yb0 = (int)c->brickYb0, yb1 = yb0 + (int)c->brickRowsY, zb0 = (int)c->brickZb0, zb1 = zb0 + (int)c->brickPlanesZ;
 	const int own0 = (int)(alongY ? c->yBegin : c->zBegin) / 16, own1 = (int)(alongY ? c->yEnd : c->zEnd) / 16;
 	c->cellMapStale = true;
-	mat_store_invalidate(c);
+	kept_state_invalidate(c);
 	auto layers = [&](int l0, int l1) {
 		if (l1 <= l0) return;
 		const int box[4] = { alongY ? l0 : yb0, alongY ? l1 : yb1, alongY ? zb0 : l0, alongY ? zb1 : l1 };
@@ -1462,7 +1488,7 @@ int vx_halo_exchange(vx_ctx* c)
 	if (!ok) return fail(c, VX_ERR_DEVICE, "vx_halo_exchange: " + c->be.error());
 	c->be.run_halo_moves(pl.hasLo ? &pl.recvLo : nullptr, pl.hasHi ? &pl.recvHi : nullptr, halo_view(c), mirror_state(c), alongY);
 	c->cellMapStale = true; // (the unpack writes the received rows into the bricks: the cells of the last owned block layer read them)
-	mat_store_invalidate(c); // (... and the received flags and material rows are what the votes of that layer read)
+	kept_state_invalidate(c); // (... and the received flags and material rows are what the votes of that layer read)
 	refresh_halo_layers(c);
 	c->haveSurface = false;
 	return VX_OK;
@@ -1496,7 +1522,7 @@ int vx_halo_exchange_group(vx_ctx* const* ctxs, int count)
 		if (!c->be.sync_ok()) return fail(c, VX_ERR_DEVICE, "vx_halo_exchange_group: copy failed: " + c->be.error());
 		c->be.run_halo_moves(plans[(size_t)i].hasLo ? &plans[(size_t)i].recvLo : nullptr, plans[(size_t)i].hasHi ? &plans[(size_t)i].recvHi : nullptr, halo_view(c), mirror_state(c), c->slabAxis == 2);
 		c->cellMapStale = true;
-		mat_store_invalidate(c);
+		kept_state_invalidate(c);
 		refresh_halo_layers(c);
 		c->haveSurface = false;
 	}
@@ -1511,7 +1537,7 @@ int vx_grid_update_blocks(vx_ctx* c, uint32_t count, const uint32_t* ids, const 
 	const u32 n = c->n, nb = n / 16;
 	bool ok = true;
 	for (u32 i = 0; i < count; ++i) if (ids[i] >= nb * nb * nb) return fail(c, VX_ERR_INVALID, "vx_grid_update_blocks: block id out of range");
-	mat_store_invalidate(c); // (also where only the flags change: the skip flags of level-0 blocks mask their cells out of the votes)
+	kept_state_invalidate(c); // (also where only the flags change: the skip flags of level-0 blocks mask their cells out of the votes)
 	if (count && (dist || mat || blend)) {
 		// the blocks travel as they are (4096 contiguous bytes each) and are scattered into the dense fields on the device
 		const size_t bytes = (size_t)count * 4096;
@@ -1676,10 +1702,25 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 			c->runEpoch = 1;
 		}
 		// the set the previous run's last kernel left in its start state, if it did (then this run has no k_reset)
-		const bool clean = c->otherSetClean;
-		if (clean) select_run_set(c, c->runSet ^ 1u);
-		c->otherSetClean = false;
+		bool clean = c->cleanSet >= 0;
 		ExecParams p;
+		bool planRun = false, kept = false; // this attempt may leave a slot plan behind | runs on the one that is there
+#if defined(VX_BACKEND_SLOT_PLAN) && !defined(VX_CASE_DUMP)
+		// An assigning attempt or a kept one?  Kept: the plan is valid for this level count, the attempt is one of the runs that
+		// may leave one (full, single-stream, reading the cell map, timed by the device clock - what it is known to be before a set
+		// is chosen: none of this depends on the set), and the tail of the run before has seeded a set of counters for it.
+		fill_params(c, p, levels);
+		planRun = c->planOn && c->dCellMap && !(first_meshed_level && c->be.partial_applies(p, levels)) && c->be.single_stream(p, levels)
+		          && !hostTiming && RunClock::applies(c->be, p, levels);
+		kept = planRun && c->planValid && c->planLevels == levels && c->seedSet >= 0;
+		if (!kept) slot_plan_drop(c); // (whoever hands out slots overwrites the plan's)
+		++c->planRuns[kept ? 1 : 0];
+		c->be.keepSlots = kept;
+#endif
+		const int cleanKept = c->cleanSet;
+		if (kept) { clean = true; select_run_set(c, (u32)c->seedSet, c->mapSet); } // (the clean set and the clean maps stay what they are)
+		else if (clean) select_run_set(c, (u32)c->cleanSet, c->mapSet ^ 1u);
+		c->cleanSet = c->seedSet = -1;
 		fill_params(c, p, levels);
 		// a partial run (first_meshed_level > 0) exists on the single-stream path only; anything else meshes every level and says so
 		emitFrom = (first_meshed_level && c->be.partial_applies(p, levels)) ? std::min<u32>(first_meshed_level, levels) : 0u;
@@ -1726,10 +1767,21 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 		c->be.stage_mark(0);
 		c->be.tailDone = (u32*)c->dHeader + HDR_PUBLISHED + 1; // (k_tail's count of finished general workgroups)
 		c->be.run_reset(p, levels, (u32*)c->dHeader, HDR_WORDS, (u32*)c->dListCounts, c->listWgs, clean); // header = 0, slot maps = -1, list counts = 0
+		u32 nextClean = 0, nextSeed = 0;
 		{
 			u32 ids[MAX_LEVELS];
 			for (u32 L = 0; L < MAX_LEVELS; ++L) ids[L] = L < c->refLevels ? c->lv[L].cnt * c->lv[L].cnt * c->lv[L].cnt : 0u;
-			c->be.set_next_reset((u32*)c->headerSet[c->runSet ^ 1u], HDR_WORDS, (u32*)c->listCountSet[c->runSet ^ 1u], c->listWgs, c->upperMaps[c->runSet ^ 1u], ids);
+			// what the run's last kernel prepares: for an assigning run behind it a set of counters and the other set of maps ...
+			nextClean = c->headerSet[2] ? (c->runSet + 1u) % 3u : c->runSet ^ 1u;
+			if (!kept) c->be.set_next_reset((u32*)c->headerSet[nextClean], HDR_WORDS, (u32*)c->listCountSet[nextClean], c->listWgs, c->upperMaps[c->mapSet ^ 1u], ids);
+#if defined(VX_BACKEND_SLOT_PLAN)
+			// ... and for a run that keeps this run's slots the third set, seeded.  A kept run prepares only that: the clean set
+			// and the clean maps are still as the last assigning run's tail left them, and the plan's maps stay as they are.
+			if (kept) { c->be.nextReset.header = nullptr; nextClean = cleanKept >= 0 ? (u32)cleanKept : nextClean; }
+			nextSeed = 3u - c->runSet - nextClean;
+			c->be.nextSeed.header = nullptr;
+			if (planRun) c->be.set_next_seed((u32*)c->headerSet[nextSeed], HDR_WORDS, (u32*)c->listCountSet[nextSeed], c->listWgs, (const u32*)c->dHeader, levels, HDR_LARGE + 1, HDR_STATS + 2);
+#endif
 		}
 #if defined(VX_CASE_DUMP)
 		for (u32 L = 0; L < levels; ++L) { c->be.fill(c->lv[L].caseDump, 0, (size_t)c->lv[L].cap * BLOCK_CELLS); c->be.fill(c->lv[L].trCaseDump, 0, (size_t)c->lv[L].cap * TR_CELLS * 2); }
@@ -1762,7 +1814,10 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 			published = c->be.lists_publish_header(c->hdrPinned, (const u32*)c->dHeader, HDR_WORDS + partials, (u32*)c->dHeader + HDR_PUBLISHED);
 			RunClock::tag(c->be, HDR_PUBLISHED, c->runEpoch, byClock ? (u32)HDR_CLOCK1 : 0u);
 			published = c->be.run_block_lists(p, plan, levels) && published;
-			c->otherSetClean = c->be.tailCleaned;
+			c->cleanSet = c->be.tailCleaned ? (int)nextClean : (kept ? cleanKept : -1);
+#if defined(VX_BACKEND_SLOT_PLAN)
+			c->seedSet = c->be.tailSeeded ? (int)nextSeed : -1;
+#endif
 			c->be.stage_mark(7);
 		}
 		if (!byClock) c->be.end_timing_record();
@@ -1796,6 +1851,11 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 		t3 = tNow();
 		const u32 usedV = c->hdr[HDR_CURSORS], usedI = c->hdr[HDR_CURSORS + CUR_I], overflow = c->hdr[HDR_CURSORS + CUR_OVF];
 		if (c->hdr[HDR_GIVEUP]) return fail(c, VX_ERR_DEVICE, "vx_polygonize: a dependency wait inside the upper pass timed out (internal error)");
+#if defined(VX_BACKEND_SLOT_PLAN)
+		// The attempt's head has handed out its slots and its tail has seeded the counters of a run that keeps them: from here
+		// on there is a plan - whether or not this attempt is accepted, its slots are what every repeat would hand out again.
+		if (planRun && !kept && c->seedSet >= 0) { c->planValid = true; c->planLevels = levels; }
+#endif
 #if defined(VX_BACKEND_MAT_STORE)
 		// a replayed block without an entry in the store (an unchanged grid has none): the store is dropped, the run repeated as a voting one
 		if (c->be.matModeUsed == 2u && c->hdr[HDR_STATS + STAT_MAT_MISS]) { mat_store_invalidate(c); c->be.matModeUsed = 0; continue; }
@@ -2000,6 +2060,7 @@ int vx_polygonize_dirty(vx_ctx* c, const float min_corner[3], const float max_co
 	if (!c->haveSurface) return fail(c, VX_ERR_INVALID, "vx_polygonize_dirty: run vx_polygonize first");
 	if (c->zBegin != 0 || c->zEnd != c->n || c->yBegin != 0 || c->yEnd != c->n) return fail(c, VX_ERR_INVALID, "vx_polygonize_dirty: not supported on slabs");
 	const u32 levels = c->levelsRun;
+	slot_plan_drop(c); // (an incremental run hands out slots of its own, and rewrites skip and ntCount of the blocks it touches)
 	auto tNow = []() { return std::chrono::steady_clock::now(); };
 	auto tUs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count() * 1e-3; };
 	const auto t0 = tNow(); // (VX_HOST_TIMING: where the call's host time goes)
@@ -2550,6 +2611,16 @@ int vx_material_path_counts(vx_ctx* c, uint32_t out[2])
 	out[0] = c->hdr[HDR_STATS + STAT_MAT_PATHS]; out[1] = c->hdr[HDR_STATS + STAT_MAT_PATHS + 1];
 	return VX_OK;
 }
+
+#if defined(VX_BACKEND_SLOT_PLAN)
+int vx_slot_plan_counts(vx_ctx* c, uint64_t out[2])
+{
+	VX_ENTER_RUN(c); // (host counters)
+	if (!c || !out) return fail(c, VX_ERR_INVALID, "vx_slot_plan_counts: null argument");
+	out[0] = c->planRuns[0]; out[1] = c->planRuns[1];
+	return VX_OK;
+}
+#endif
 
 int vx_transition_path_counts(vx_ctx* c, uint32_t out[2])
 {

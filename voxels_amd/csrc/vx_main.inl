@@ -76,10 +76,13 @@ struct MainPlan {
 // write the bitmaps of their level-0 children, which no level-0 walk forms in such a run.
 // MAP (full runs with the level-0 queue only): the cell map is current - nobody forms a bitmap.
 template <bool DIRTY, bool PARTIAL = false, bool MAP = false>
-__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_main(ExecParamsDev pArg, MainPlan plan)
+// clockStart: a run without k_run_head (the slot plan, vx_host.inl) - workgroup 0 leaves the 100 MHz clock here as it starts, the
+// start of the run's device_ms (include/voxels_hip.h: "the first workgroup of the run"); nullptr in every other run.
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_main(ExecParamsDev pArg, MainPlan plan, u32* clockStart)
 {
 #define MAIN_PARAMS() (void)pArg; const ExecParamsDev& p = kernarg_params() // (vx_hip.hip: read afresh, per item)
 	MAIN_PARAMS();
+	if (clockStart && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(clockStart, run_clock(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (read by the publishing workgroup of k_tail, possibly on another XCD)
 	u8* tab = smem;
 	u8* state = smem + UP_TAB_LDS;
 	// (one 16-byte aligned block of statics in front of the dynamic region: its base stays aligned for the 16-byte LDS accesses)
