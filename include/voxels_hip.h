@@ -512,6 +512,87 @@ int  vx_record_read_block(vx_ctx* ctx, const vx_record* record, uint32_t index, 
 void vx_record_free(vx_ctx* ctx, vx_record* record);
 int  vx_brush_box(const vx_brush* brush, uint32_t n, vx_box* out);
 
+/* ---- stamps (HIP library only) ------------------------------------------------------------------------------------------
+ * Copy part of the resident grid and put it somewhere else, or place a prefab kept as voxels, without a trip through the host.
+ * A STAMP is a device-resident dense copy of a voxel box: a size (sx, sy, sz) and three byte fields - distance, material,
+ * blend - x fastest, then y, then z (internal axes, Z up).  It belongs to the context that made it and does not depend on the
+ * grid's edge.  A PASTE puts a stamp into the grid at an integer origin, in one of the eight orientations that keep Z up, under
+ * one of four combine modes; vx_grid_paste applies an ordered batch of them in one device pass.  Everything is integer and every
+ * byte of the result is defined.  voxels_amd/csrc/tv_stamp.h is the per-voxel logic; tests/stamp_oracle.py states this text
+ * again in numpy.  Needs a context that owns a whole grid (vx_grid_upload / vx_grid_upload_packed / vx_grid_create_*), as the
+ * brushes.
+ *   Capture    vx_stamp_capture copies the voxels of `box` ([lo, hi), grid coordinates) out of the dense fields (the mirrors
+ *              play no part).  BF_Empty flags are not part of a stamp.  The call never changes the grid, the flags, the mirrors
+ *              or any kept state: a full run afterwards replays what it replayed before.
+ *   Upload     vx_stamp_upload makes a stamp from host arrays of size[0] * size[1] * size[2] bytes each; mat and blend may be
+ *              NULL: zeros.
+ *   Reading    vx_stamp_read (every output may be NULL); vx_stamp_info_get.
+ *   Orient     vx_paste.orient is 0..7.  Bit 2 mirrors the stamp's x first: i' = sx-1-i.  Bits 0..1 are q quarter turns about
+ *              +z, counter-clockwise seen from +z.  Stamp voxel (i, j, k) has the oriented coordinates (u, v, k):
+ *                q = 0: (i', j)      q = 1: (sy-1-j, i')      q = 2: (sx-1-i', sy-1-j)      q = 3: (j, sx-1-i')
+ *              The oriented size is (sy, sx, sz) for odd q, otherwise (sx, sy, sz).  Grid voxel = origin + (u, v, k): origin is
+ *              the min corner of the oriented stamp, any int32; the part outside [0, n)^3 is clipped (64-bit arithmetic).
+ *   Modes      per voxel, the grid holds (d, m, b) and the stamp (sd, sm, sb):
+ *                VX_PASTE_REPLACE    (sd, sm, sb)
+ *                VX_PASTE_UNION      (sd, sm, sb) if sd < d, otherwise unchanged
+ *                VX_PASTE_SUBTRACT   c = (sd == -128 ? 127 : -sd); d = c if c > d; m and b stay
+ *                VX_PASTE_PAINT      (d, sm, sb) if sd < 0, otherwise unchanged
+ *   Order      the grid afterwards is byte for byte what `count` single-paste calls in array order leave.
+ *   Blocks     the touched blocks of a paste are the blocks its clipped box intersects.  BF_Empty is recomputed by the codec's
+ *              rule for every block that at least one paste of a mode other than VX_PASTE_PAINT touches, and for no other block
+ *              (the brushes' rule).  The brick mirrors follow over the distinct touched blocks: a polygonization afterwards
+ *              needs no vx_grid_invalidate.  A batch that touches no block launches nothing that writes and changes nothing.
+ *   Results    results[i] (may be NULL): box = the clipped voxel box, all zeros when the paste misses the grid; touched_blocks =
+ *              the number of blocks of that box.  counts (may be NULL): out_min / out_max, changed_voxels, changed_blocks and
+ *              flag_changes have the meaning and the convention of vx_swap_result - the box is over the voxels that differ
+ *              between the grid before and after the whole batch, output order (x, z, y), [a, b + 1] clamped, zeros when
+ *              nothing differed; feed it to vx_polygonize_dirty with no margin - and touched_blocks is the number of distinct
+ *              touched blocks.
+ *   Boxes      vx_paste_box (host only, no context): the clipped box by the same integer expressions, for a grid of edge n.
+ *              1 = the paste touches the grid, 0 = it misses it (the box is zeroed: leave it out).  Capturing the boxes of a
+ *              paste array with vx_grid_capture captures exactly the touched blocks.
+ *   Lifetime   vx_stamp_free releases a stamp (NULL is legal); vx_ctx_destroy frees what is left.  A stamp survives runs,
+ *              vx_compact_pools, edits and the upload of another grid, of any edge.
+ * Everything is checked before anything is launched: VX_ERR_INVALID, with nothing changed, for a null context, out pointer or
+ * info, a null array with a non-zero count, a box with lo >= hi or hi > n, a size of 0, above VX_STAMP_MAX_EDGE or with a
+ * product above VX_STAMP_MAX_VOXELS, a null dist in upload, count > VX_PASTE_MAX_COUNT, n_stamps > VX_PASTE_MAX_STAMPS,
+ * stamp >= n_stamps, a null entry that a paste refers to (an unreferenced null entry is legal), a stamp of another context,
+ * orient > 7, mode > 3, non-zero reserved words, a context that does not own a whole grid (capture, paste).  vx_paste_box
+ * returns VX_ERR_INVALID for a null argument, a zero size, orient > 7 or an n that is not a multiple of 16 in 16..2048.
+ * VX_ERR_DEVICE, with the grid untouched, when memory cannot be allocated.  count = 0 is VX_OK.
+ * All calls are synchronous and run on the context's stream (vx_set_stream): capture and upload do not wait for the device,
+ * vx_grid_paste waits once, at its end, vx_stamp_read waits for its copies.
+ * Memory: 3 bytes per voxel of device memory, in one allocation per stamp; vx_stamp_info.bytes is that product.  Working memory
+ * of a batch, kept with the context and only ever grown: 32 bytes per paste, 24 per stamp of the array, 8 per block of the grid,
+ * 12 per distinct touched block and 4 per (paste, block) pair, in chunks of at most 2^22 pairs; a batch that needs several chunks
+ * adds 12 bytes per block of the grid and 12 289 per block that more than one chunk touches. */
+typedef struct vx_stamp vx_stamp;                       /* opaque; belongs to the context that made it */
+typedef struct vx_stamp_info { uint32_t size[3], reserved; uint64_t voxels, bytes; } vx_stamp_info;   /* 32 bytes */
+#define VX_STAMP_MAX_EDGE   2048u
+#define VX_STAMP_MAX_VOXELS (1u << 30)
+#define VX_PASTE_REPLACE  0u
+#define VX_PASTE_UNION    1u
+#define VX_PASTE_SUBTRACT 2u
+#define VX_PASTE_PAINT    3u
+#define VX_PASTE_MAX_COUNT  (1u << 20)
+#define VX_PASTE_MAX_STAMPS (1u << 16)
+typedef struct vx_paste { int32_t origin[3]; uint32_t stamp; uint32_t orient; uint32_t mode; uint32_t reserved[2]; } vx_paste;   /* 32 bytes */
+typedef struct vx_paste_result { vx_box box; uint32_t touched_blocks, reserved; } vx_paste_result;                             /* 32 bytes */
+typedef struct vx_paste_counts { float out_min[3], out_max[3]; uint64_t changed_voxels;
+                                 uint32_t changed_blocks, flag_changes, touched_blocks, reserved; } vx_paste_counts;           /* 48 bytes */
+int  vx_stamp_capture(vx_ctx* ctx, const vx_box* box /* host */, vx_stamp** out);
+int  vx_stamp_upload(vx_ctx* ctx, const uint32_t size[3], const int8_t* dist, const uint8_t* mat /* may be NULL: zeros */,
+                     const uint8_t* blend /* may be NULL: zeros */, vx_stamp** out);
+int  vx_stamp_read(vx_ctx* ctx, const vx_stamp* stamp, int8_t* dist, uint8_t* mat, uint8_t* blend);
+int  vx_stamp_info_get(vx_ctx* ctx, const vx_stamp* stamp, vx_stamp_info* info);
+void vx_stamp_free(vx_ctx* ctx, vx_stamp* stamp);
+int  vx_grid_paste(vx_ctx* ctx, vx_stamp* const* stamps, uint32_t n_stamps, const vx_paste* pastes /* host */, uint32_t count,
+                   vx_paste_result* results /* may be NULL */, vx_paste_counts* counts /* may be NULL */);
+int  vx_paste_box(const vx_paste* paste, const uint32_t stamp_size[3], uint32_t n, vx_box* out);
+/* tests: the capacity of the (paste, block) lists of this context's batches, 0 = the default (2^22); nothing of a batch's
+ * result depends on it */
+int  vx_debug_paste_list_cap(vx_ctx* ctx, uint32_t capacity);
+
 /* MaterialMap::GetMaterial resolved on the host (include/MaterialMap.h:19-30): lut[id] = {DiffuseIds0[3],
  * DiffuseIds1[3]}, valid[id] == 0 means GetMaterial returned NULL (texture bytes stay 0). */
 int vx_material_lut(vx_ctx* ctx, const uint8_t* lut /*256*6*/, const uint8_t* valid /*256*/);

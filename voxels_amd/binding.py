@@ -67,6 +67,15 @@ RECORD_INFO_DTYPE = np.dtype([("n", "<u4"), ("blocks", "<u4"), ("bytes", "<u8"),
 SWAP_RESULT_DTYPE = np.dtype([("out_min", "<f4", 3), ("out_max", "<f4", 3), ("changed_voxels", "<u8"), ("changed_blocks", "<u4"), ("flag_changes", "<u4"),
                               ("reserved", "<u8")])
 assert BOX_DTYPE.itemsize == 24 and RECORD_INFO_DTYPE.itemsize == 48 and SWAP_RESULT_DTYPE.itemsize == 48
+# stamps (include/voxels_hip.h, "stamps")
+STAMP_INFO_DTYPE = np.dtype([("size", "<u4", 3), ("reserved", "<u4"), ("voxels", "<u8"), ("bytes", "<u8")])
+PASTE_DTYPE = np.dtype([("origin", "<i4", 3), ("stamp", "<u4"), ("orient", "<u4"), ("mode", "<u4"), ("reserved", "<u4", 2)])
+PASTE_RESULT_DTYPE = np.dtype([("box", BOX_DTYPE), ("touched_blocks", "<u4"), ("reserved", "<u4")])
+PASTE_COUNTS_DTYPE = np.dtype([("out_min", "<f4", 3), ("out_max", "<f4", 3), ("changed_voxels", "<u8"), ("changed_blocks", "<u4"), ("flag_changes", "<u4"),
+                               ("touched_blocks", "<u4"), ("reserved", "<u4")])
+assert STAMP_INFO_DTYPE.itemsize == 32 and PASTE_DTYPE.itemsize == 32 and PASTE_RESULT_DTYPE.itemsize == 32 and PASTE_COUNTS_DTYPE.itemsize == 48
+STAMP_MAX_EDGE, STAMP_MAX_VOXELS, PASTE_MAX_COUNT, PASTE_MAX_STAMPS = 2048, 1 << 30, 1 << 20, 1 << 16
+PASTE_REPLACE, PASTE_UNION, PASTE_SUBTRACT, PASTE_PAINT = 0, 1, 2, 3
 RECORD_MAX_BLOCKS = 1 << 18
 RECORD_MAX_BOXES = 1 << 16
 SPHERE_STARTED_IN_CONTACT = 1
@@ -335,6 +344,20 @@ class HipLibrary:
             lib.vx_brush_box.argtypes = [vp, u32, vp]
             for name in ("vx_grid_capture", "vx_record_trim", "vx_record_swap", "vx_record_info_get", "vx_record_block_ids", "vx_record_read_block", "vx_brush_box"):
                 getattr(lib, name).restype = C.c_int
+        # stamps: HIP builds only, likewise
+        stamp_calls = ("vx_stamp_capture", "vx_stamp_upload", "vx_stamp_read", "vx_stamp_info_get", "vx_grid_paste", "vx_paste_box")
+        self.has_stamps = all(hasattr(lib, name) for name in stamp_calls + ("vx_stamp_free",))
+        if self.has_stamps:
+            lib.vx_stamp_capture.argtypes = [vp, vp, C.POINTER(vp)]
+            lib.vx_stamp_upload.argtypes = [vp, vp, vp, vp, vp, C.POINTER(vp)]
+            lib.vx_stamp_read.argtypes = [vp, vp, vp, vp, vp]
+            lib.vx_stamp_info_get.argtypes = [vp, vp, vp]
+            lib.vx_stamp_free.argtypes = [vp, vp]
+            lib.vx_stamp_free.restype = None
+            lib.vx_grid_paste.argtypes = [vp, vp, u32, vp, u32, vp, vp]
+            lib.vx_paste_box.argtypes = [vp, vp, u32, vp]
+            for name in stamp_calls:
+                getattr(lib, name).restype = C.c_int
         self.has_lod = hasattr(lib, "vx_lod_select")
         if self.has_lod:
             lib.vx_lod_select_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
@@ -428,6 +451,35 @@ def brush_boxes(brushes, n, library=None):
     return out[keep]
 
 
+def pastes(rows):
+    """a PASTE_DTYPE array from one, or from rows of (origin, stamp, orient, mode)"""
+    if isinstance(rows, np.ndarray) and rows.dtype == PASTE_DTYPE:
+        return np.ascontiguousarray(rows).reshape(-1)
+    p = np.zeros(len(rows), PASTE_DTYPE)
+    for k, (origin, stamp, orient, mode) in enumerate(rows):
+        p[k]["origin"], p[k]["stamp"], p[k]["orient"], p[k]["mode"] = np.asarray(origin, np.int32), stamp, orient, mode
+    return p
+
+
+def paste_boxes(paste_rows, sizes, n, library=None):
+    """vx_paste_box over a PASTE_DTYPE array; sizes = the (sx, sy, sz) of every stamp of the stamp array: the BOX_DTYPE array of the
+    pastes that touch a grid of edge n, in array order - capture it before vx_grid_paste and the record holds exactly the blocks
+    the batch touches"""
+    L = library or HipLibrary()
+    if not L.has_stamps:
+        raise VoxelsHipError("this library has no stamps (HIP builds only)")
+    ps = pastes(paste_rows)
+    sizes = np.ascontiguousarray(sizes, np.uint32).reshape(-1, 3)
+    out = np.zeros(ps.size, BOX_DTYPE)
+    keep = np.zeros(ps.size, bool)
+    for k in range(ps.size):
+        rc = L.lib.vx_paste_box(_ptr(ps[k:k + 1]), _ptr(sizes[int(ps[k]["stamp"])]), int(n), _ptr(out[k:k + 1]))
+        if rc < 0:
+            raise VoxelsHipError("vx_paste_box failed (%d)" % rc)
+        keep[k] = rc == 1
+    return out[keep]
+
+
 def capsule_stroke(p0, p1, radius, inj_type=2, margin=2.0):
     """One capsule brush for a tool of `radius` moved from p0 to p1 (grid coordinates, Z up): positioned at the middle of the
     segment, the ends relative to it, rewriting the segment's box grown by radius + margin on every side."""
@@ -504,6 +556,45 @@ class Record:
         if self._r and getattr(self._p, "_h", None):
             self._p._lib.vx_record_free(self._p._h, self._r)
         self._r = None
+
+    def __del__(self):
+        self.free()
+
+
+class Stamp:
+    """A stamp (include/voxels_hip.h, "stamps") of a Polygonizer: made by Polygonizer.capture_stamp / upload_stamp, freed by
+    free() or when it is collected while the polygonizer that owns it lives."""
+
+    def __init__(self, poly, handle):
+        self._p, self._s = poly, handle
+
+    def _call(self, fn, *args):
+        if not self._s:
+            raise VoxelsHipError("the stamp has been freed")
+        p = self._p
+        p._check(getattr(p._lib, fn)(p._h, self._s, *args), fn)
+
+    def info(self):
+        """vx_stamp_info_get -> the STAMP_INFO_DTYPE record"""
+        info = np.zeros(1, STAMP_INFO_DTYPE)
+        self._call("vx_stamp_info_get", _ptr(info))
+        return info[0]
+
+    @property
+    def size(self):
+        return tuple(int(v) for v in self.info()["size"])
+
+    def read(self):
+        """vx_stamp_read -> (dist int8[sz, sy, sx], mat, blend)"""
+        sx, sy, sz = self.size
+        d, m, b = np.zeros((sz, sy, sx), np.int8), np.zeros((sz, sy, sx), np.uint8), np.zeros((sz, sy, sx), np.uint8)
+        self._call("vx_stamp_read", _ptr(d), _ptr(m), _ptr(b))
+        return d, m, b
+
+    def free(self):
+        if self._s and getattr(self._p, "_h", None):
+            self._p._lib.vx_stamp_free(self._p._h, self._s)
+        self._s = None
 
     def __del__(self):
         self.free()
@@ -641,6 +732,41 @@ class Polygonizer:
         h = C.c_void_p()
         self._check(self._lib.vx_grid_capture(self._h, _ptr(b) if b.size else None, b.size, C.byref(h)), "vx_grid_capture")
         return Record(self, h)
+
+    def capture_stamp(self, box):
+        """vx_stamp_capture: the voxels of box = (lo, hi) in grid coordinates (internal axes, Z up) -> a Stamp"""
+        if not self._L.has_stamps:
+            raise VoxelsHipError("this library has no stamps (HIP builds only)")
+        b = boxes([box])
+        h = C.c_void_p()
+        self._check(self._lib.vx_stamp_capture(self._h, _ptr(b), C.byref(h)), "vx_stamp_capture")
+        return Stamp(self, h)
+
+    def upload_stamp(self, dist, mat=None, blend=None):
+        """vx_stamp_upload: dist int8 [sz, sy, sx] (and mat, blend uint8 of the same shape, None = zeros) -> a Stamp"""
+        if not self._L.has_stamps:
+            raise VoxelsHipError("this library has no stamps (HIP builds only)")
+        dist = np.ascontiguousarray(dist, np.int8)
+        assert dist.ndim == 3
+        mat, blend = (None if a is None else np.ascontiguousarray(a, np.uint8) for a in (mat, blend))
+        assert all(a is None or a.shape == dist.shape for a in (mat, blend))
+        size = np.array(dist.shape[::-1], np.uint32)
+        h = C.c_void_p()
+        self._check(self._lib.vx_stamp_upload(self._h, _ptr(size), _ptr(dist), _ptr(mat), _ptr(blend), C.byref(h)), "vx_stamp_upload")
+        return Stamp(self, h)
+
+    def paste(self, stamps, paste_rows):
+        """vx_grid_paste: a list of Stamps (None entries allowed) and a PASTE_DTYPE array (or rows of (origin, stamp, orient, mode))
+        applied in array order in one device pass -> (results PASTE_RESULT_DTYPE array, counts PASTE_COUNTS_DTYPE record)"""
+        if not self._L.has_stamps:
+            raise VoxelsHipError("this library has no stamps (HIP builds only)")
+        ps = pastes(paste_rows)
+        handles = (C.c_void_p * max(len(stamps), 1))(*[None if s is None else s._s for s in stamps])
+        results = np.zeros(ps.size, PASTE_RESULT_DTYPE)
+        counts = np.zeros(1, PASTE_COUNTS_DTYPE)
+        self._check(self._lib.vx_grid_paste(self._h, C.cast(handles, C.c_void_p) if len(stamps) else None, len(stamps), _ptr(ps) if ps.size else None, ps.size,
+                                            _ptr(results) if ps.size else None, _ptr(counts)), "vx_grid_paste")
+        return results, counts[0]
 
     def islands(self, box=None, detached_only=False, remove=False, anchor_faces=0x3F, max_voxels=0, air_value=127, labels=None, capacity=None):
         """vx_grid_islands: the connected components of the solid voxels of `box` ((lo, hi), None = the whole grid) ->

@@ -259,7 +259,7 @@ __global__ __launch_bounds__(WG) void k_brush_apply(GridView g, u8* flags, Brush
 			}
 		}
 	}
-	if (t == 0) { runs = 0; p.count[id] = 0; } // the counter is clean for the next chunk and the next call
+	if (t == 0) p.count[id] = 0; // the counter is clean for the next chunk and the next call
 	__syncthreads();
 
 	const uint4 raw = ((const uint4*)sDist)[t];
@@ -270,44 +270,9 @@ __global__ __launch_bounds__(WG) void k_brush_apply(GridView g, u8* flags, Brush
 	}
 	if (!anyDist) return; // (uniform) blocks that only material brushes touch keep their flag
 
-	// BF_Empty by the codec's rule, as k_edit_flags of vx_hip.hip counts it, from the LDS copy: a run starts where the value
-	// changes and every 255 voxels inside a constant stretch; empty <=> at most 2048 runs and every sample has strictly the
-	// sign of the first.
-	i8 v[16];
-	memcpy(v, &raw, 16);
-	lastOfRow[t] = v[15];
-	__syncthreads();
-	const i8 first = sDist[0];
-	i8 prev = t ? lastOfRow[t - 1] : (i8)~v[0]; // voxel 0 always starts a run
-	int lastStart = -1;
-	bool sameSign = true;
-#pragma unroll
-	for (int j = 0; j < 16; ++j) {
-		if (v[j] != prev) lastStart = (int)t * 16 + j;
-		prev = v[j];
-		sameSign = sameSign && ((int)first * (int)v[j] > 0);
-	}
-	int incl = lastStart;
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if ((int)(t & 63) >= d) incl = max(incl, o); }
-	if ((t & 63) == 63) waveMax[t >> 6] = incl;
-	__syncthreads();
-	int carry = __shfl_up(incl, 1);
-	if ((t & 63) == 0) carry = -1;
-	for (u32 w = 0; w < (t >> 6); ++w) carry = max(carry, waveMax[w]);
-	u32 myRuns = 0;
-	int start = carry;
-	prev = t ? lastOfRow[t - 1] : (i8)~v[0];
-#pragma unroll
-	for (int j = 0; j < 16; ++j) {
-		const int pos = (int)t * 16 + j;
-		if (v[j] != prev) start = pos;
-		prev = v[j];
-		if ((pos - start) % 255 == 0) ++myRuns;
-	}
-	if (myRuns) atomicAdd(&runs, myRuns);
-	const int allSame = __syncthreads_and(sameSign ? 1 : 0);
-	if (t == 0) flags[id] = (allSame && runs <= 2048u) ? 1 : 0;
+	// BF_Empty by the codec's rule from the LDS copy (block_empty_rows of vx_hip.hip, as k_edit_flags)
+	const bool empty = block_empty_rows(raw, sDist[0], t, lastOfRow, waveMax, &runs);
+	if (t == 0) flags[id] = empty ? 1 : 0;
 }
 
 // host: the blocks of one axis that a brush touches.  The test of edit_touched_box is monotone in the block (the first

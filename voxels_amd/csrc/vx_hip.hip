@@ -453,24 +453,17 @@ __global__ __launch_bounds__(WG) void k_box_ids(u32* out, u32 x0, u32 y0, u32 z0
 	out[i] = (z * nb + y) * nb + x;
 }
 
-// BF_Empty by the codec's rule (edit_block_empty of tv_block.h walks the block serially), one workgroup per block.
-// A run starts where the value changes and every 255 voxels inside a constant stretch; the RLE stays "effective"
-// while it has at most 2048 runs; empty <=> effective and every sample has strictly the sign of the first.
-__global__ __launch_bounds__(WG) void k_edit_flags(GridView g, u8* flags, const u32* ids, u32 count)
+// BF_Empty by the codec's rule (edit_block_empty of tv_block.h walks the block serially) by a whole workgroup: lane t holds row t
+// of the block = (y = t & 15, z = t >> 4), 16 voxels in codec order, `first` is voxel 0.  A run starts where the value changes
+// and every 255 voxels inside a constant stretch; the RLE stays "effective" while it has at most 2048 runs; empty <=> effective
+// and every sample has strictly the sign of the first.  The three arrays are LDS of the caller; the result is uniform.
+__device__ __forceinline__ bool block_empty_rows(const uint4 raw, i8 first, u32 t, i8* lastOfRow /* [WG] */, int* waveMax /* [WG / 64] */, u32* runs)
 {
-	__shared__ i8 lastOfRow[WG];
-	__shared__ int waveMax[WG / 64];
-	__shared__ u32 runs;
-	const u32 nb = (u32)g.n / 16, id = ids ? ids[blockIdx.x] : blockIdx.x, t = threadIdx.x; // no list = every block
-	const u32 bx = id % nb, by = (id / nb) % nb, bz = id / (nb * nb);
-	const i8* base = g.dist + dist_offset(g, (int)(bx * 16), (int)(by * 16), (int)(bz * 16)); // whole grids and slabs alike
-	const uint4 raw = *(const uint4*)(base + ((size_t)(t >> 4) * g.pitchY + (t & 15)) * g.n); // row t = (y = t & 15, z = t >> 4): codec order
 	i8 v[16];
 	memcpy(v, &raw, 16);
 	lastOfRow[t] = v[15];
-	if (t == 0) runs = 0;
+	if (t == 0) *runs = 0;
 	__syncthreads();
-	const i8 first = base[0];
 	i8 prev = t ? lastOfRow[t - 1] : (i8)~v[0]; // voxel 0 always starts a run
 	int lastStart = -1;                         // last position in this row where the value changes
 	bool sameSign = true;
@@ -499,9 +492,23 @@ __global__ __launch_bounds__(WG) void k_edit_flags(GridView g, u8* flags, const 
 		prev = v[j];
 		if ((pos - start) % 255 == 0) ++myRuns;
 	}
-	if (myRuns) atomicAdd(&runs, myRuns);
+	if (myRuns) atomicAdd(runs, myRuns);
 	const int allSame = __syncthreads_and(sameSign ? 1 : 0);
-	if (t == 0) flags[id] = (allSame && runs <= 2048u) ? 1 : 0;
+	return allSame && *runs <= 2048u;
+}
+
+// BF_Empty of the listed blocks, one workgroup per block.
+__global__ __launch_bounds__(WG) void k_edit_flags(GridView g, u8* flags, const u32* ids, u32 count)
+{
+	__shared__ i8 lastOfRow[WG];
+	__shared__ int waveMax[WG / 64];
+	__shared__ u32 runs;
+	const u32 nb = (u32)g.n / 16, id = ids ? ids[blockIdx.x] : blockIdx.x, t = threadIdx.x; // no list = every block
+	const u32 bx = id % nb, by = (id / nb) % nb, bz = id / (nb * nb);
+	const i8* base = g.dist + dist_offset(g, (int)(bx * 16), (int)(by * 16), (int)(bz * 16)); // whole grids and slabs alike
+	const uint4 raw = *(const uint4*)(base + ((size_t)(t >> 4) * g.pitchY + (t & 15)) * g.n); // row t = (y = t & 15, z = t >> 4): codec order
+	const bool empty = block_empty_rows(raw, base[0], t, lastOfRow, waveMax, &runs);
+	if (t == 0) flags[id] = empty ? 1 : 0;
 }
 
 // k_copy_segments: pool compaction — segment i moves `count` elements from src[srcOff] to dst[dstOff]; elements are
@@ -4333,6 +4340,7 @@ struct Backend {
 #include "vx_host.inl"
 #include "vx_undo.inl"
 #include "vx_brush.inl"
+#include "vx_stamp.inl"
 #include "vx_island.inl"
 #include "vx_smooth.inl"
 #include "vx_walk.inl"

@@ -200,6 +200,9 @@ struct vx_ctx {
 	// overlap queries (vx_overlap.inl): its device buffers
 	void* overlapState = nullptr;
 	void (*overlapFree)(vx_ctx*) = nullptr;
+	// stamps (vx_stamp.inl): the stamps the context owns and the device buffers of its paste batches
+	void* stampState = nullptr;
+	void (*stampFree)(vx_ctx*) = nullptr;
 };
 
 // What only a backend with a device clock and a header the host can wait on offers (VX_BACKEND_HEADER_WAIT, defined by the
@@ -940,6 +943,7 @@ void vx_ctx_destroy(vx_ctx* c)
 	if (c->walkFree) c->walkFree(c);
 	if (c->undoFree) c->undoFree(c);
 	if (c->overlapFree) c->overlapFree(c);
+	if (c->stampFree) c->stampFree(c);
 	c->be.shutdown();
 	delete c;
 }
