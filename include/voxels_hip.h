@@ -1009,11 +1009,21 @@ int vx_stats(vx_ctx* ctx, uint32_t stats[20]);
 int vx_transition_path_counts(vx_ctx* ctx, uint32_t out[2]);
 
 /* Material blocks (active blocks of the levels >= 1) of the last full run by how their material cache came about (both 0
- * behind an incremental run, which counts none): out[0] = voted from the children, out[1] = replayed from the material store - what the last full single-stream run on this grid
- * left, copied where nothing the votes read has changed since (distances, materials, blends, BF_Empty flags, the context's
- * range).  VX_MATSTORE=0 (read at context creation) keeps no store: every run votes.  Diagnostics: caches, meshes and
- * statistics are the same either way. */
+ * behind an incremental run, which counts none): out[0] = voted from the children, out[1] = replayed - taken over from the
+ * run that filled the material store (the last full single-stream run on this grid) where nothing the votes read has changed
+ * since (distances, materials, blends, BF_Empty flags, the context's range): either copied from the store into the block's
+ * slot or, in a run that keeps the slot plan (vx_slot_plan_counts), left in the slot, which still holds it.
+ * VX_MATSTORE=0 (read at context creation) keeps no store: every run votes.  VX_MAT_INPLACE=0 (read at context creation)
+ * leaves nothing in place: a run that keeps the slot plan copies from the store like every other replaying run.
+ * Diagnostics: caches, meshes and statistics are the same either way. */
 int vx_material_path_counts(vx_ctx* ctx, uint32_t out[2]);
+
+/* Full-run attempts of this context (since it was created) whose material blocks were replayed, by how: out[0] = copied from
+ * the material store into their slots (a run that hands out its slots, or VX_MAT_INPLACE=0), out[1] = left in place (a run
+ * that keeps the slot plan: its upper queue has no material items, and its regular and transition blocks wait for nobody).
+ * Attempts that voted count in neither.  Diagnostics: caches, meshes, statistics and vx_material_path_counts are the same
+ * either way.  HIP builds only. */
+int vx_material_inplace_counts(vx_ctx* ctx, uint64_t out[2]);
 
 /* Full runs of this context (every attempt of vx_polygonize / vx_polygonize_from, since the context was created) by where their
  * slots came from: out[0] = handed out by the run itself (k_run_head, or the classification pass of the chain of launches),

@@ -288,6 +288,11 @@ class HipLibrary:
         self.has_slot_plan = hasattr(lib, "vx_slot_plan_counts")
         if self.has_slot_plan:
             lib.vx_slot_plan_counts.argtypes = [vp, vp]
+        # (material caches left in place by the runs that keep the plan: HIP builds only - the CPU emulation has neither store
+        # nor plan - and absent from builds made before it)
+        self.has_material_inplace = hasattr(lib, "vx_material_inplace_counts")
+        if self.has_material_inplace:
+            lib.vx_material_inplace_counts.argtypes = [vp, vp]
         lib.vx_selftest.argtypes = [vp, vp]
         lib.vx_stage_layout.argtypes = [vp, C.POINTER(C.c_int)]
         lib.vx_set_stage_timing.argtypes = [vp, C.c_int]
@@ -1275,4 +1280,13 @@ class Polygonizer:
             raise VoxelsHipError("this library has no vx_slot_plan_counts")
         out = np.zeros(2, np.uint64)
         self._check(self._lib.vx_slot_plan_counts(self._h, _ptr(out)), "vx_slot_plan_counts")
+        return int(out[0]), int(out[1])
+
+    def material_inplace_counts(self):
+        """vx_material_inplace_counts: (copied, left in place) - the full-run attempts of this context whose material blocks were
+        replayed, by how, cumulative.  HIP builds only: the CPU emulation library has no such entry point."""
+        if not self._L.has_material_inplace:
+            raise VoxelsHipError("this library has no vx_material_inplace_counts")
+        out = np.zeros(2, np.uint64)
+        self._check(self._lib.vx_material_inplace_counts(self._h, _ptr(out)), "vx_material_inplace_counts")
         return int(out[0]), int(out[1])

@@ -49,15 +49,16 @@ typedef BrickSamplerT<u32> F1BrickSampler; // valid while a mirror is smaller th
 // One block of a level 1..3 (CAP = LDS capacity class; `lo`: blocks with at most that many non-trivial cells belong to a lower
 // class).  GATED (k_main): bitmap, cache block and cell count come from the material work of another workgroup of the same
 // launch; the lattice samples, which do not, are requested before the wait.  Otherwise (k_regular1_fast) `ntc` and `coord`
-// come from the run's flat list.
+// come from the run's flat list.  `gated` (uniform, run time; GATED only): false = a run in place (MainPlan::matMode 3) - the
+// slot holds what an earlier launch wrote, `ntc` is the caller's, nothing is waited for and the loads are ordinary ones.
 template <int CAP, bool GATED>
 __device__ __forceinline__ void f1_block(const ExecParamsDev& p, const F0Tables& T, const F1BrickSampler& smp, Fast1State<CAP>& st, u32* wgStats, u32* zeroFlag, u32& parity,
-                                         u32 level, u32 slot, u32 coord, u32 ntc, u32 lo, const int tid)
+                                         u32 level, u32 slot, u32 coord, u32 ntc, u32 lo, const int tid, const bool gated = GATED)
 {
 	typedef R0<CAP> K;
 	const u32 lane = (u32)tid & 63u, wave = (u32)tid >> 6;
 	const LevelDesc& L = p.levels[level];
-	if (!GATED) {
+	if (!GATED || !gated) {
 		if (ntc > (u32)CAP || (lo && ntc <= lo)) return;    // another capacity class owns those (the first class, lo == 0, also owns the empty blocks)
 		if (ntc == 0) {                                     // (uniform) a surface-bearing block without a non-trivial coarse cell
 			if (tid == 0) reg_write_empty_record(L, slot);
@@ -81,7 +82,7 @@ __device__ __forceinline__ void f1_block(const ExecParamsDev& p, const F0Tables&
 	const u16* csrc = L.cache + (size_t)slot * BLOCK_CELLS;
 	u32 bitsWord = 0;
 	uint4 c0, c1;
-	if (GATED) {
+	if (GATED && gated) {
 		// the flag carries this run's tag or the wait goes on: no word of an older run is ever taken for the cell count
 		if (tid == 0) st.zero = wait_done(L.matDone + slot, p.G.epoch, p.G.giveUp);
 		acquire_and_meet(tid < 64);
@@ -92,8 +93,13 @@ __device__ __forceinline__ void f1_block(const ExecParamsDev& p, const F0Tables&
 			return;
 		}
 	}
-	bitsWord = TV_LOAD_THROUGH(&L.ntBits[(size_t)slot * 128 + (tid & 127)]);
-	c0 = load16_through(csrc, (u32)tid * 16u); c1 = load16_through(csrc, (u32)(tid + WG) * 16u);
+	if (GATED && !gated) { // (uniform) in place: requested together with the lattice rows
+		bitsWord = L.ntBits[(size_t)slot * 128 + (tid & 127)];
+		c0 = ((const uint4*)csrc)[tid]; c1 = ((const uint4*)csrc)[tid + WG];
+	} else {
+		bitsWord = TV_LOAD_THROUGH(&L.ntBits[(size_t)slot * 128 + (tid & 127)]);
+		c0 = load16_through(csrc, (u32)tid * 16u); c1 = load16_through(csrc, (u32)(tid + WG) * 16u);
+	}
 
 	// ---- stage: bitmap, material cache block, 17 x 17 rows of 17 lattice samples; any zero among them? -------------
 	{

@@ -2412,12 +2412,15 @@ template <bool WIDE, bool GATED>
 __device__ __forceinline__ void tr_block(const ExecParamsDev& p, RegBlockCtx b, u32 coordId, TrState& st, const Tables& T, u32* scanScratch, u32* quietFaces, u32& quietParity,
                                          const BrickSamplerT<typename std::conditional<WIDE, size_t, u32>::type>& smp, int tid, const bool tables, u32* pathCount, const bool matKnown = true)
 {
-	// matKnown: the block's material cache is known to be complete (the stand-alone pass: earlier launches wrote it): its entries
-	// behind the transition cells are then requested with the planes.  (Inside k_main that would need a launch-wide "all
-	// material blocks published" counter: measured, the counter's hot line cost the material blocks more than the round trip
-	// saved here.)
+	// matKnown: the block's material cache is known to be complete - earlier launches wrote it (the stand-alone pass; inside
+	// k_main a run in place, MainPlan::matMode 3): nothing is waited for.  In the stand-alone pass its entries behind the
+	// transition cells are also requested with the planes (preMat).  Inside k_main they are fetched where they are used, with
+	// or without a wait in front: staging them with the planes in a run in place (measured, eight alternating bench rounds,
+	// profiles/inplace_ab_bench.txt) read 0.3066 ms per step against 0.3039 with the late fetch.  (With a wait, staging early would
+	// need a launch-wide "all material blocks published" counter: measured, the counter's hot line cost the material blocks
+	// more than the round trip saved here.)
 	bool matReady = !GATED || matKnown;
-	const bool preMat = matReady;
+	const bool preMat = !GATED;
 	const LevelDesc& L = p.levels[b.level];
 	b.mult = L.mult;
 	block_coords(__builtin_amdgcn_readfirstlane(coordId), L.cnt, b.bx, b.by, b.bz);
@@ -3358,6 +3361,7 @@ struct Backend {
 		u32 cellMap = 1;     // VX_CELLMAP=0: no cell map - the level-0 blocks of a single-stream run form their own bitmaps, its level-1 material blocks their children's
 		u32 matStore = 1;    // VX_MATSTORE=0: no material store - every full run votes the material caches of the levels >= 1
 		u32 plan = 1;        // VX_PLAN=0: no slot plan - every full run launches k_run_head
+		u32 matInPlace = 1;  // VX_MAT_INPLACE=0: a run that keeps the slot plan still copies the material caches from the store into their slots
 		// fixed since round 6 (were environment variables while they were being measured; profiles/HISTORY.md has the sweeps)
 		static constexpr u32 classifyRowGroup = 4, regWgsPerCu = 20, f1WgsPerCu = 20, foldBlocks = 65536, upWgsPerCu = 5, mainWgsPerCu = 4, mainBatch = 2, mainUpperNum = 1, mainUpperDen = 4;
 		bool fast0() const { return (fast & 1u) != 0; }
@@ -3394,6 +3398,7 @@ struct Backend {
 		tune.cellMap = env_u32("VX_CELLMAP", 1);
 		tune.matStore = env_u32("VX_MATSTORE", 1);
 		tune.plan = env_u32("VX_PLAN", 1);
+		tune.matInPlace = env_u32("VX_MAT_INPLACE", 1);
 		hipDeviceProp_t prop;
 		if (hipGetDeviceProperties(&prop, device) == hipSuccess) cus = prop.multiProcessorCount;
 		if (!check(hipStreamCreateWithFlags(&ownStream, hipStreamNonBlocking), "hipStreamCreate")) { err = lastError; return false; }
@@ -3486,7 +3491,8 @@ struct Backend {
 	// ... and the material store?  Where it keeps the cell map: only the runs that read the map capture and replay.
 	bool wants_mat_store(u32 n) const { return tune.matStore && wants_cell_map(n); }
 	// what the host asks of the next k_main of the cell-map form (MainPlan::matMode), and what the last run_main launched: the
-	// host learns from it whether the attempt it accepts was one that captured or replayed
+	// host learns from it whether the attempt it accepts was one that captured or replayed (1 capture, 2 copy from the store,
+	// 3 in place: a run that keeps the slot plan leaves the caches in their slots)
 	u32 matMode = 0, matModeUsed = 0;
 	// the cell map of the level-0 blocks [yb0, yb1) x [zb0, zb1) (all x) from the brick mirror and the sign summaries
 	void run_cell_map(const GridView& g, const MirrorState& ms, u32 yb0, u32 yb1, u32 zb0, u32 zb1)
@@ -4013,8 +4019,11 @@ struct Backend {
 		plan.batch = tune.mainBatch;
 		plan.trTables = tune.fastT() ? 1u : 0u;
 		plan.upperNum = withLevel0 ? tune.mainUpperNum : 1u; plan.upperDen = withLevel0 ? tune.mainUpperDen : 1u;
-		unsigned long long items = 0; // at most: one material item per block, one regular, one transition
-		for (u32 l = 1; l < levels; ++l) items += (unsigned long long)p.levels[l].cap * (1u + (l < plan.fastEnd ? 1u : 0u) + (p.levels[l].hasTransitions ? 1u : 0u));
+		// the cell-map form's material mode; in place only for a run that keeps its slots (the host asks for it on no other one)
+		const bool mapForm = withLevel0 && !emitFrom && p.G.cellMap;
+		const u32 mode = (mapForm && p.G.matStore[1].index) ? ((matMode == 3u && !keepSlots) ? 2u : matMode) : 0u;
+		unsigned long long items = 0; // at most: one material item per block (none in place), one regular, one transition
+		for (u32 l = 1; l < levels; ++l) items += (unsigned long long)p.levels[l].cap * ((mode == 3u ? 0u : 1u) + (l < plan.fastEnd ? 1u : 0u) + (p.levels[l].hasTransitions ? 1u : 0u));
 		if (withLevel0) items += p.levels[0].cap;
 		matModeUsed = 0;
 		if (!items) return;
@@ -4027,7 +4036,7 @@ struct Backend {
 			plan.level0 = 0u; plan.upperNum = plan.upperDen = 1u; plan.emitFrom = emitFrom;
 			launch_with_event(k_main<false, true>, dim3(grid), UP_TAB_LDS + MAIN_STATE_LDS, dev(p), plan, (u32*)nullptr);
 		} else if (withLevel0 && p.G.cellMap) {
-			plan.matMode = p.G.matStore[1].index ? matMode : 0u;
+			plan.matMode = mode;
 			matModeUsed = plan.matMode;
 			// (a run that keeps its slots has no head: the run's clock starts here)
 			launch_with_event(k_main<false, false, true>, dim3(grid), UP_TAB_LDS + MAIN_STATE_LDS, dev(p), plan, keepSlots ? clockStart : (u32*)nullptr);

@@ -86,6 +86,11 @@ struct vx_ctx {
 	std::vector<void*> matStoreAllocs;
 	bool matStoreValid = false;
 	u32 matStoreLevels = 0;
+	// A replaying attempt that also keeps the slot plan (below) leaves the caches in their slots instead of copying them there
+	// (MainPlan::matMode 3; VX_MAT_INPLACE=0 keeps the copy).  matReplayRuns: full-run attempts with a replaying store whose
+	// material blocks were copied | left in place (vx_material_inplace_counts).
+	bool matInPlaceOn = false;
+	uint64_t matReplayRuns[2] = { 0, 0 };
 	void* dListCounts = nullptr;                         // listed blocks per LIST_WG block coordinates, all levels (LevelDesc::listCounts)
 	// Two sets of what a full run needs in its start state - the header's counters, the block -> slot maps of the levels >= 1,
 	// the list counts: a run works on one set, and its last kernel (k_tail) resets the other for the run behind it, which then
@@ -899,6 +904,8 @@ int vx_ctx_create(int device_index, vx_ctx** out)
 #if defined(VX_BACKEND_SLOT_PLAN)
 	// VX_PLAN=0: no slot plan, two sets of counters - every full run launches k_run_head
 	c->planOn = c->be.tune.plan != 0;
+	// VX_MAT_INPLACE=0: a run that keeps the plan still runs the store's copy items
+	c->matInPlaceOn = c->be.tune.matInPlace != 0;
 	if (c->planOn) c->headerSet[2] = c->be.alloc((HDR_WORDS + HDR_PARTIALS) * 4);
 	if (c->planOn && !c->headerSet[2]) { vx_ctx_destroy(c); return VX_ERR_DEVICE; }
 #endif
@@ -1699,10 +1706,13 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 	auto tUs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count() * 1e-3; };
 	const auto t0 = tNow();
 	auto t1 = t0, t2 = t0, t3 = t0;
+	// An attempt that fails - a device error, a header that did not arrive, a dependency wait that gave up - may have left slots
+	// half written: neither the slot plan nor the material store outlives it (a later run hands out slots and votes).
+	auto fail_run = [c](int code, const std::string& msg) { kept_state_invalidate(c); return fail(c, code, msg); };
 	for (;;) {
 		// every attempt gets a tag of its own for the dependency flags of the upper pass; on wrap-around the flags start over
 		if (++c->runEpoch == 0) {
-			for (u32 L = 1; L < c->refLevels && L < MAX_LEVELS; ++L) if (c->lv[L].matDone && !c->be.fill(c->lv[L].matDone, 0, (size_t)c->lv[L].cap * 8)) return fail(c, VX_ERR_DEVICE, "vx_polygonize: flag reset failed");
+			for (u32 L = 1; L < c->refLevels && L < MAX_LEVELS; ++L) if (c->lv[L].matDone && !c->be.fill(c->lv[L].matDone, 0, (size_t)c->lv[L].cap * 8)) return fail_run(VX_ERR_DEVICE, "vx_polygonize: flag reset failed");
 			c->runEpoch = 1;
 		}
 		// the set the previous run's last kernel left in its start state, if it did (then this run has no k_reset)
@@ -1713,6 +1723,19 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 		// An assigning attempt or a kept one?  Kept: the plan is valid for this level count, the attempt is one of the runs that
 		// may leave one (full, single-stream, reading the cell map, timed by the device clock - what it is known to be before a set
 		// is chosen: none of this depends on the set), and the tail of the run before has seeded a set of counters for it.
+		//
+		// What a kept attempt may also rely on (the material caches in place, matMode 3 below): every slot of the levels
+		// 1 .. levels - 1 holds the cache block, bitmap and cell count (LevelDesc::cache, ntBits, ntCount) and the flat item
+		// (Globals::flatItems) that the attempt which left the plan wrote there.  The writers of those four, all of them:
+		//   * mat_block in k_main<false, false, true> (a vote, or a vote that captures) and mat_copy_block (the store's copy): the
+		//     material items of the attempt that left the plan and of every kept attempt since that was not in place.  Functions
+		//     of the grid, the flags and the slot alone: they write the same bytes every time.  A copy that found no entry
+		//     (STAT_MAT_MISS) wrote an empty cache: the store is invalidated for it, so the repeat votes and cannot be in place;
+		//   * mat_block in k_main<false> and k_main<false, true> (no cell map, partial runs), in k_material (the chain of launches)
+		//     and in k_main<true> (incremental runs): none of them is a planRun, and vx_polygonize_dirty drops the plan itself;
+		//   * ensure_level_tables, which allocates them: free_level_tables invalidates plan and store.
+		// Every change of the grid's contents, flags or range invalidates both (kept_state_invalidate), and so does an attempt
+		// that fails (fail_run above).  No other kernel and no copy writes a level >= 1's cache, bitmap or cell count or the flat list.
 		fill_params(c, p, levels);
 		planRun = c->planOn && c->dCellMap && !(first_meshed_level && c->be.partial_applies(p, levels)) && c->be.single_stream(p, levels)
 		          && !hostTiming && RunClock::applies(c->be, p, levels);
@@ -1746,8 +1769,8 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 #if defined(VX_BACKEND_MAT_STORE)
 		// The same runs - and only they - capture into the material store or replay from it.  Replay: the store is valid (nothing
 		// it depends on has changed since a run filled it) and covers the run's levels.  Otherwise this attempt captures: the store
-		// is invalid from here on and becomes valid again behind the loop, when the attempt that was accepted is known to have
-		// been a capturing one (its header arrived without HDR_GIVEUP: every material item has completed).
+		// is invalid from here on and becomes valid again below, when a capturing attempt is known to have completed every
+		// material item (its header arrived without HDR_GIVEUP and it is not repeated with the large capacity class).
 		c->be.matMode = c->be.matModeUsed = 0; // (matModeUsed: set by the launch of k_main's cell-map form, if this attempt has one)
 		if (p.G.cellMap && ensure_mat_store(c)) {
 			const bool replay = c->matStoreValid && levels <= c->matStoreLevels;
@@ -1755,11 +1778,19 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 				mat_store_invalidate(c);
 				for (u32 L = 1; L < levels; ++L) {
 					const size_t total = (size_t)c->lv[L].cnt * c->lv[L].cnt * c->lv[L].cnt;
-					if (!c->be.fill(c->matStore[L].index, 0xFF, total * 4)) return fail(c, VX_ERR_DEVICE, "vx_polygonize: material store reset failed");
+					if (!c->be.fill(c->matStore[L].index, 0xFF, total * 4)) return fail_run(VX_ERR_DEVICE, "vx_polygonize: material store reset failed");
 				}
 			}
 			for (u32 L = 1; L < levels; ++L) p.G.matStore[L] = c->matStore[L];
-			c->be.matMode = replay ? 2u : 1u;
+			// A replaying attempt that also keeps the slot plan copies nothing: the copy's destination holds the copy's source.
+			// The attempt that left the plan ran a material item for every slot of the levels 1 .. levels - 1 - a vote, a
+			// capturing vote or a copy, which write the same cache block, bitmap, cell count and flat item - every kept attempt
+			// since wrote them again unchanged or left them alone, and whatever else writes them drops the plan (the list where
+			// `kept` is decided).  An attempt that left empty caches behind (STAT_MAT_MISS) invalidates the store below, so its
+			// repeat votes; a failed attempt leaves neither plan nor store (fail_run).
+			const bool inPlace = replay && kept && c->matInPlaceOn;
+			c->be.matMode = replay ? (inPlace ? 3u : 2u) : 1u;
+			if (replay) ++c->matReplayRuns[inPlace ? 1 : 0];
 		}
 #endif
 		// device time: two clock words of the header on the single-stream path; the event pair on the chain of launches, with
@@ -1810,7 +1841,7 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 			plan.totals = (u32*)c->dHeader + HDR_LISTS;
 			// the header reaches the host with the run's last kernel (HeaderPublish) - or as a copy behind it
 			if (!c->hdrPinned) c->hdrPinned = (u32*)c->be.alloc_pinned((HDR_WORDS + HDR_PARTIALS) * 4);
-			if (!c->hdrPinned) { c->be.sync(); c->be.end_overlapped(); return fail(c, VX_ERR_DEVICE, "vx_polygonize: pinned allocation failed"); }
+			if (!c->hdrPinned) { c->be.sync(); c->be.end_overlapped(); return fail_run(VX_ERR_DEVICE, "vx_polygonize: pinned allocation failed"); }
 			partials = std::min<u32>(c->be.head_partials(), (u32)HDR_PARTIALS);
 			// (the run before has published, or was waited for: nobody else writes this word now.  Its value when the header has
 			// arrived is this attempt's tag, which is not 0 and not the tag of the attempt before.)
@@ -1826,7 +1857,7 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 		}
 		if (!byClock) c->be.end_timing_record();
 		RunClock::start_word(c->be, nullptr);
-		if (byClock && !published) { c->be.sync(); c->be.end_overlapped(); return fail(c, VX_ERR_DEVICE, "vx_polygonize: a single-stream run without a published header (internal error)"); }
+		if (byClock && !published) { c->be.sync(); c->be.end_overlapped(); return fail_run(VX_ERR_DEVICE, "vx_polygonize: a single-stream run without a published header (internal error)"); }
 		bool okRun = published || c->be.d2h_async(c->hdrPinned, c->dHeader, (HDR_WORDS + partials) * 4); // (one host wait per run either way)
 		t1 = tNow();
 		if (okRun && byClock && RunClock::waits_for_header(c->be)) {
@@ -1842,8 +1873,8 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 		}
 		c->be.end_overlapped(); // (the tail of an overlapped run was queued on a side stream)
 		t2 = tNow();
-		if (!okRun) return fail(c, VX_ERR_DEVICE, "vx_polygonize: device run failed: " + c->be.error());
-		if (published && __atomic_load_n(c->hdrPinned + HDR_PUBLISHED, __ATOMIC_ACQUIRE) != c->runEpoch) return fail(c, VX_ERR_DEVICE, "vx_polygonize: the run's header did not arrive (internal error)");
+		if (!okRun) return fail_run(VX_ERR_DEVICE, "vx_polygonize: device run failed: " + c->be.error());
+		if (published && __atomic_load_n(c->hdrPinned + HDR_PUBLISHED, __ATOMIC_ACQUIRE) != c->runEpoch) return fail_run(VX_ERR_DEVICE, "vx_polygonize: the run's header did not arrive (internal error)");
 		ms = byClock ? RunClock::ms(c->be, c->hdrPinned[HDR_CLOCK0], c->hdrPinned[HDR_CLOCK1]) : c->be.elapsed_ms();
 		memcpy(c->hdr, c->hdrPinned, HDR_WORDS * 4);
 		if (partials) { // the block-class statistics arrive as per-workgroup partial sums behind the header (k_run_head)
@@ -1854,7 +1885,7 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 		}
 		t3 = tNow();
 		const u32 usedV = c->hdr[HDR_CURSORS], usedI = c->hdr[HDR_CURSORS + CUR_I], overflow = c->hdr[HDR_CURSORS + CUR_OVF];
-		if (c->hdr[HDR_GIVEUP]) return fail(c, VX_ERR_DEVICE, "vx_polygonize: a dependency wait inside the upper pass timed out (internal error)");
+		if (c->hdr[HDR_GIVEUP]) return fail_run(VX_ERR_DEVICE, "vx_polygonize: a dependency wait inside the upper pass timed out (internal error)");
 #if defined(VX_BACKEND_SLOT_PLAN)
 		// The attempt's head has handed out its slots and its tail has seeded the counters of a run that keeps them: from here
 		// on there is a plan - whether or not this attempt is accepted, its slots are what every repeat would hand out again.
@@ -1865,6 +1896,12 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 		if (c->be.matModeUsed == 2u && c->hdr[HDR_STATS + STAT_MAT_MISS]) { mat_store_invalidate(c); c->be.matModeUsed = 0; continue; }
 #endif
 		if (c->hdr[HDR_LARGE] && !c->be.largeClass) { c->be.largeClass = true; continue; } // blocks of the large class showed up: once more, with it
+#if defined(VX_BACKEND_MAT_STORE)
+		// The attempt captured: its header arrived without HDR_GIVEUP, so every material item has completed and the store is
+		// filled - whether or not the meshes fitted the pools (no material item touches them).  A repeat for larger pools
+		// replays, then, and on the slots this attempt handed out it does so in place.
+		if (c->be.matModeUsed == 1u) { c->matStoreValid = true; c->matStoreLevels = levels; }
+#endif
 		if (!overflow) break;
 		if (++retries > 3) return fail(c, VX_ERR_OVERFLOW, "vx_polygonize: output pools keep overflowing");
 		settle_run(c); // (the pools are freed)
@@ -1872,7 +1909,6 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 	}
 	c->be.emitFrom = 0;
 #if defined(VX_BACKEND_MAT_STORE)
-	if (c->be.matModeUsed == 1u) { c->matStoreValid = true; c->matStoreLevels = levels; } // (the accepted attempt captured)
 	c->be.matMode = c->be.matModeUsed = 0;
 #endif
 	c->largeHint = c->hdr[HDR_LARGE] != 0;
@@ -2622,6 +2658,14 @@ int vx_slot_plan_counts(vx_ctx* c, uint64_t out[2])
 	VX_ENTER_RUN(c); // (host counters)
 	if (!c || !out) return fail(c, VX_ERR_INVALID, "vx_slot_plan_counts: null argument");
 	out[0] = c->planRuns[0]; out[1] = c->planRuns[1];
+	return VX_OK;
+}
+
+int vx_material_inplace_counts(vx_ctx* c, uint64_t out[2])
+{
+	VX_ENTER_RUN(c); // (host counters)
+	if (!c || !out) return fail(c, VX_ERR_INVALID, "vx_material_inplace_counts: null argument");
+	out[0] = c->matReplayRuns[0]; out[1] = c->matReplayRuns[1];
 	return VX_OK;
 }
 #endif

@@ -25,6 +25,9 @@
 //     On a grid that has not changed since a full run of this form filled the material store (MatStoreLevel, tv_block.h;
 //     MainPlan::matMode) the material items are copy items (mat_copy_block): same queue position, same stores, same flag -
 //     the regular and transition items behind them notice nothing - but no samples, no vote and nobody to wait for.
+//     A run that also keeps the slot plan (matMode 3, "in place") has no material segment at all: every slot of the levels
+//     >= 1 still holds the cache, bitmap, cell count and flat item that the run which left the plan wrote there (vx_host.inl,
+//     where `kept` is decided, lists the writers), so the queue is [ regular | transition ] and nobody polls a flag.
 //   * the level-0 queue: the active level-0 slots, taken in batches of consecutive slots (x-neighbour blocks: a batch is
 //     walked with the register prefetch of f0_walk, and its blocks share halo lines in one XCD's L2).
 // A workgroup prefers one of the queues (a share of the workgroups the upper one, so that the latency-bound dependency chain
@@ -63,7 +66,9 @@ struct MainPlan {
 	u32 trTables;   // 1: transition blocks take the table-driven body where they qualify (VX_FAST bit 2; vx_fastt.inl)
 	// the material store (MAP form only; Globals::matStore is set for the run's levels where this is not 0): 1 = the material
 	// blocks vote as always and also leave their results in the store (mat_block: capture), 2 = they are copy items
-	// (mat_copy_block).  Uniform at run time: not another instantiation of the kernel.
+	// (mat_copy_block), 3 = in place: the run keeps the slot plan, and every slot still holds what the copy would write - the
+	// upper queue has no material segment, and regular and transition items read their slots with ordinary loads and no
+	// wait (the data is an earlier launch's).  Uniform at run time: not another instantiation of the kernel.
 	u32 matMode;
 };
 
@@ -111,7 +116,10 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 		if (PARTIAL && l + 1u == plan.emitFrom) skipItems = matEnd[l];
 	}
 	if (PARTIAL) { regTotal = max(regTotal, skipItems) - skipItems; trTotal = max(trTotal, skipItems) - skipItems; }
-	const u32 upperTotal = matTotal + regTotal + trTotal;
+	// (in place: matEnd still decodes a regular or transition item to (level, slot); only the segment itself leaves the queue)
+	const bool inPlace = MAP && plan.matMode == 3u;
+	const u32 matSeg = inPlace ? 0u : matTotal;
+	const u32 upperTotal = matSeg + regTotal + trTotal;
 	const u32 total0 = plan.level0 ? r0_uniform(DIRTY ? p.G.workCount[0] : p.G.slotCounts[0]) : 0u;
 
 	u32 tabKind = 0;          // which table image the LDS holds: 0 none, 1 regular (F0), 2 transition
@@ -146,8 +154,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 		const u32 item = r0_uniform(sh.nextItem[turn]);
 		if (item >= upperTotal) { upperLeft = false; continue; }
 		// item -> (kind, level, slot): the position inside its segment, looked up in the level boundaries
-		const bool isMat = item < matTotal, isReg = !isMat && item < matTotal + regTotal;
-		const u32 f = isMat ? item : ((isReg ? item - matTotal : item - matTotal - regTotal) + (PARTIAL ? skipItems : 0u));
+		const bool isMat = item < matSeg, isReg = !isMat && item < matSeg + regTotal;
+		const u32 f = isMat ? item : ((isReg ? item - matSeg : item - matSeg - regTotal) + (PARTIAL ? skipItems : 0u));
 		u32 level = 1, base = 0;
 #pragma unroll
 		for (u32 l = 1; l + 1 < MAX_LEVELS; ++l) if (f >= matEnd[l]) { level = l + 1; base = matEnd[l]; }
@@ -173,12 +181,14 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 		const F1BrickSampler smp = { g.bDist, g.bMat, g.bBlend, g.n - 1, (u32)g.n >> 4, (u32)g.bRowsY, g.bYb0, g.bZb0 };
 		if (isReg) {
 			if (tabKind != 1u) { FT = f0_stage_tables(tab, p.tables, (u32)tid); tabKind = 1u; } // (behind the barriers of the dequeue; visible after the block's first barrier)
-			f1_block<REG_CAP_SMALL, true>(p, FT, smp, *(Fast1State<REG_CAP_SMALL>*)state, wgStats, zeroFlag, parity, level, slot, coord, 0u, 0u, tid);
+			// (in place: the cell count is the slot's own, requested with the coordinate)
+			const u32 ntc = inPlace ? r0_uniform((u32)L.ntCount[slot]) : 0u;
+			f1_block<REG_CAP_SMALL, true>(p, FT, smp, *(Fast1State<REG_CAP_SMALL>*)state, wgStats, zeroFlag, parity, level, slot, coord, ntc, 0u, tid, !inPlace);
 		} else {
 			if (tabKind != 2u) { TT = stage_transition_tables(tab, p.tables, (u32)tid); tabKind = 2u; }
 			RegBlockCtx b;
 			b.level = level; b.slot = slot;
-			tr_block<false, true>(p, b, coord, *(TrState*)state, TT, scanScratch, quietFaces, quietParity, smp, tid, plan.trTables != 0u, wgStats + 2, false);
+			tr_block<false, true>(p, b, coord, *(TrState*)state, TT, scanScratch, quietFaces, quietParity, smp, tid, plan.trTables != 0u, wgStats + 2, inPlace);
 		}
 	}
 	__syncthreads();
@@ -189,7 +199,8 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 		if (tid < 20 && wgStats[tid]) atomicAdd(&p.G.stats[(tid == 2 || tid == 3) ? (int)STAT_TR_PATHS + tid - 2 : tid], wgStats[tid]);
 		// full runs: the material blocks by body (vx_material_path_counts).  Which body is the launch's (plan.matMode), so the
 		// count is the length of the queue's material segment, added once - a counter per item would be kept by every workgroup
-		if (!DIRTY && blockIdx.x == 0 && tid == 20 && matTotal) atomicAdd(&p.G.stats[STAT_MAT_PATHS + ((MAP && plan.matMode == 2u) ? 1 : 0)], matTotal);
+		// (in place the segment is not part of the queue; its blocks count as replayed all the same: left in their slots)
+		if (!DIRTY && blockIdx.x == 0 && tid == 20 && matTotal) atomicAdd(&p.G.stats[STAT_MAT_PATHS + ((MAP && plan.matMode >= 2u) ? 1 : 0)], matTotal);
 	}
 }
 
