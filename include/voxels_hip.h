@@ -593,6 +593,65 @@ int  vx_paste_box(const vx_paste* paste, const uint32_t stamp_size[3], uint32_t 
  * result depends on it */
 int  vx_debug_paste_list_cap(vx_ctx* ctx, uint32_t capacity);
 
+/* ---- measurements (HIP library only) ------------------------------------------------------------------------------------
+ * How much of what is in there: the solid volume, the tight bounds of the solid voxels and the count per material of voxel
+ * boxes of the resident grid, and what an edit removed, added and repainted, read off the undo record captured around it -
+ * a few integers per box instead of the voxels over the link.  Everything is integer and exact; no result depends on an order
+ * or a schedule.  voxels_amd/csrc/tv_measure.h is the per-row logic; tests/measure_oracle.py states this text again in numpy.
+ * Needs a context that owns a whole grid (vx_grid_upload / vx_grid_upload_packed / vx_grid_create_*), as the brushes.
+ *   Solid      a voxel whose distance sample is < 0; zero is air (the definition of vx_grid_islands).
+ *   Box        a vx_box: [lo, hi) in grid coordinates, internal axes (Z up), lo < hi <= n per axis.  A box need not be aligned
+ *              to blocks.  The boxes of a batch may overlap or repeat; every box is answered on its own.
+ *   Fields     the dense fields are what is measured; the mirrors and the BF_Empty flags play no part in the result.
+ *   Measure    vx_grid_measure: results[i] describes box i - voxels = its volume; solid_voxels; min / max = the grid
+ *              coordinates of its solid voxels per internal axis, inclusive, zeros when it holds none; materials = the number
+ *              of distinct material bytes among its solid voxels.  tallies (may be NULL): tallies[i * 256 + m] = the solid
+ *              voxels of box i whose material byte is m; the 256 entries of a box sum to its solid_voxels.
+ *   Record     vx_record_measure compares every held block of an undo record with the grid as it is now: removed_voxels are
+ *              solid in the record and not in the grid, added_voxels the other way round, repainted_voxels solid in both with
+ *              different material bytes; min / max = the inclusive bounds of the removed and the added voxels, zeros when there
+ *              are none; blocks = held blocks with a removed, added or repainted voxel.  removed[m] (may be NULL, 256 entries)
+ *              counts the removed voxels by the material the RECORD holds for them, added[m] the added voxels by the material
+ *              the GRID holds now.  A record captured before an edit so reports what the edit did.  After a vx_record_swap the
+ *              record holds the edited state and the grid the earlier one, so the same call reports the redo's effect: removed
+ *              and added exchange their roles.  An empty record gives zeros.
+ * Neither call changes the grid, the flags, the mirrors, a record or any kept state: a full run afterwards replays what it
+ * replayed before.
+ * Everything is checked before anything is launched: VX_ERR_INVALID for a null context, results, delta or record, a null box
+ * array with count > 0, count > VX_MEASURE_MAX_BOXES, lo >= hi or hi > n on any axis, a context that does not own a whole
+ * grid, a record of another context or one whose n differs from the grid's now.  count = 0 is VX_OK and writes nothing.
+ * VX_ERR_DEVICE when working memory cannot be allocated.
+ * Both calls are synchronous, run on the context's stream (vx_set_stream) and wait for the device once, at their end.  Grids up
+ * to 2048^3 are covered and every count is 64-bit: a whole-grid box holds 2^33 voxels.
+ * Working memory, kept with the context and only ever grown: 2160 bytes per box - 24 of box, 8 of running block count, 32 of
+ * count and bounds, 2048 of tallies (they exist whether or not the caller asks for them: materials is counted from them), 48 of
+ * result.  The work item is a (box, block) pair; pairs are launched in chunks of at most 2^22 and a chunk needs no memory of
+ * its own.  vx_record_measure uses 4352 bytes. */
+#define VX_MEASURE_MAX_BOXES (1u << 16)
+typedef struct vx_measure {            /* 48 bytes */
+    uint64_t voxels;                   /* volume of the box */
+    uint64_t solid_voxels;
+    uint32_t min[3], max[3];           /* grid coordinates of the solid voxels, inclusive; zeros when solid_voxels == 0 */
+    uint32_t materials;                /* distinct material bytes among the solid voxels */
+    uint32_t reserved;                 /* 0 */
+} vx_measure;
+int  vx_grid_measure(vx_ctx* ctx, const vx_box* boxes /* host */, uint32_t count, vx_measure* results /* host, count entries */,
+                     uint64_t* tallies /* host, count * 256, may be NULL */);
+typedef struct vx_record_delta {       /* 64 bytes */
+    uint64_t removed_voxels;           /* solid in the record, not solid in the grid now */
+    uint64_t added_voxels;             /* not solid in the record, solid in the grid now */
+    uint64_t repainted_voxels;         /* solid in both, material bytes differ */
+    uint32_t min[3], max[3];           /* inclusive bounds of the removed and added voxels; zeros when there are none */
+    uint32_t blocks;                   /* held blocks with a removed, added or repainted voxel */
+    uint32_t reserved[3];              /* 0 */
+} vx_record_delta;
+int  vx_record_measure(vx_ctx* ctx, const vx_record* record, vx_record_delta* delta,
+                       uint64_t* removed /* host, 256, may be NULL */, uint64_t* added /* host, 256, may be NULL */);
+/* tests: the (box, block) pairs per launch of this context's measurements, 0 = the default (2^22), and whether the per-block
+ * sign summaries may stand in for distance rows (the default: yes); nothing of a result depends on either */
+int  vx_debug_measure_chunk(vx_ctx* ctx, uint32_t pairs);
+int  vx_debug_measure_shortcuts(vx_ctx* ctx, uint32_t enable);
+
 /* MaterialMap::GetMaterial resolved on the host (include/MaterialMap.h:19-30): lut[id] = {DiffuseIds0[3],
  * DiffuseIds1[3]}, valid[id] == 0 means GetMaterial returned NULL (texture bytes stay 0). */
 int vx_material_lut(vx_ctx* ctx, const uint8_t* lut /*256*6*/, const uint8_t* valid /*256*/);

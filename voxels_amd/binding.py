@@ -78,6 +78,12 @@ STAMP_MAX_EDGE, STAMP_MAX_VOXELS, PASTE_MAX_COUNT, PASTE_MAX_STAMPS = 2048, 1 <<
 PASTE_REPLACE, PASTE_UNION, PASTE_SUBTRACT, PASTE_PAINT = 0, 1, 2, 3
 RECORD_MAX_BLOCKS = 1 << 18
 RECORD_MAX_BOXES = 1 << 16
+# measurements (include/voxels_hip.h, "measurements")
+MEASURE_DTYPE = np.dtype([("voxels", "<u8"), ("solid_voxels", "<u8"), ("min", "<u4", 3), ("max", "<u4", 3), ("materials", "<u4"), ("reserved", "<u4")])
+RECORD_DELTA_DTYPE = np.dtype([("removed_voxels", "<u8"), ("added_voxels", "<u8"), ("repainted_voxels", "<u8"), ("min", "<u4", 3), ("max", "<u4", 3),
+                               ("blocks", "<u4"), ("reserved", "<u4", 3)])
+assert MEASURE_DTYPE.itemsize == 48 and RECORD_DELTA_DTYPE.itemsize == 64
+MEASURE_MAX_BOXES = 1 << 16
 SPHERE_STARTED_IN_CONTACT = 1
 # vx_lod_params / vx_lod_draw / vx_draw_indexed / vx_lod_counts (include/voxels_hip.h, LOD selection)
 LOD_PARAMS_DTYPE = np.dtype([("camera", "<f4", 3), ("n_planes", "<u4"), ("planes", "<f4", (6, 4)), ("ranges", "<f4", 16)])
@@ -363,6 +369,16 @@ class HipLibrary:
             lib.vx_paste_box.argtypes = [vp, vp, u32, vp]
             for name in stamp_calls:
                 getattr(lib, name).restype = C.c_int
+        # measurements: HIP builds only, likewise
+        measure_calls = ("vx_grid_measure", "vx_record_measure", "vx_debug_measure_chunk", "vx_debug_measure_shortcuts")
+        self.has_measure = all(hasattr(lib, name) for name in measure_calls)
+        if self.has_measure:
+            lib.vx_grid_measure.argtypes = [vp, vp, u32, vp, vp]
+            lib.vx_record_measure.argtypes = [vp, vp, vp, vp, vp]
+            lib.vx_debug_measure_chunk.argtypes = [vp, u32]
+            lib.vx_debug_measure_shortcuts.argtypes = [vp, u32]
+            for name in measure_calls:
+                getattr(lib, name).restype = C.c_int
         self.has_lod = hasattr(lib, "vx_lod_select")
         if self.has_lod:
             lib.vx_lod_select_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
@@ -557,6 +573,16 @@ class Record:
         self._call("vx_record_read_block", int(index), _ptr(d), _ptr(m), _ptr(b), _ptr(f))
         return d, m, b, int(f[0])
 
+    def measure(self, tallies=True):
+        """vx_record_measure: what changed between the record and the grid as it is now -> (the RECORD_DELTA_DTYPE record,
+        removed uint64[256] by the record's materials, added uint64[256] by the grid's); tallies=False: (delta, None, None)"""
+        if not self._p._L.has_measure:
+            raise VoxelsHipError("this library has no measurements (HIP builds only)")
+        delta = np.zeros(1, RECORD_DELTA_DTYPE)
+        removed, added = (np.zeros(256, np.uint64), np.zeros(256, np.uint64)) if tallies else (None, None)
+        self._call("vx_record_measure", _ptr(delta), _ptr(removed), _ptr(added))
+        return delta[0], removed, added
+
     def free(self):
         if self._r and getattr(self._p, "_h", None):
             self._p._lib.vx_record_free(self._p._h, self._r)
@@ -737,6 +763,18 @@ class Polygonizer:
         h = C.c_void_p()
         self._check(self._lib.vx_grid_capture(self._h, _ptr(b) if b.size else None, b.size, C.byref(h)), "vx_grid_capture")
         return Record(self, h)
+
+    def measure(self, box_rows, tallies=True):
+        """vx_grid_measure: a BOX_DTYPE array (or rows of (lo, hi)) -> (the MEASURE_DTYPE array, uint64[count, 256] solid voxels
+        per box and material byte, or None with tallies=False)"""
+        if not self._L.has_measure:
+            raise VoxelsHipError("this library has no measurements (HIP builds only)")
+        b = boxes(box_rows)
+        results = np.zeros(b.size, MEASURE_DTYPE)
+        per_material = np.zeros((b.size, 256), np.uint64) if tallies else None
+        self._check(self._lib.vx_grid_measure(self._h, _ptr(b) if b.size else None, b.size, _ptr(results) if b.size else None,
+                                              _ptr(per_material) if tallies and b.size else None), "vx_grid_measure")
+        return results, per_material
 
     def capture_stamp(self, box):
         """vx_stamp_capture: the voxels of box = (lo, hi) in grid coordinates (internal axes, Z up) -> a Stamp"""

@@ -20,7 +20,7 @@ def _newer(target, sources):
 def build_hip(force=False, verbose=True):
     """hipcc --offload-arch=gfx950 ... -o voxels_amd/csrc/libvoxels_hip.so (cross-compiles without a GPU)."""
     out = os.path.join(CSRC, "libvoxels_hip.so")
-    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_overlap.inl", "tv_overlap.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_walk.inl", "tv_walk.h", "vx_undo.inl", "tv_undo.h", "vx_stamp.inl", "tv_stamp.h", "vx_lod.inl", "tv_lod.h", "vx_scatter.inl", "tv_scatter.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
+    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_overlap.inl", "tv_overlap.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_walk.inl", "tv_walk.h", "vx_undo.inl", "tv_undo.h", "vx_stamp.inl", "tv_stamp.h", "vx_measure.inl", "tv_measure.h", "vx_lod.inl", "tv_lod.h", "vx_scatter.inl", "tv_scatter.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
     srcs.append(os.path.join(ROOT, "include", "voxels_hip.h"))
     if not force and not _newer(out, srcs):
         return out
@@ -44,7 +44,8 @@ def build_hip(force=False, verbose=True):
                            "k_scatter_count", "k_scatter_scan", "k_scatter_write",
                            "k_overlap_count", "k_overlap_scan", "k_overlap_write",
                            "k_rec_mark", "k_rec_scan", "k_rec_list", "k_rec_capture", "k_rec_diff", "k_rec_pack", "k_rec_swap",
-                           "k_stamp_capture", "k_paste_count", "k_paste_fill", "k_paste_apply")
+                           "k_stamp_capture", "k_paste_count", "k_paste_fill", "k_paste_apply",
+                           "k_measure_pairs", "k_measure_finish", "k_rec_measure")
                if not any(k in name and "ScratchSize" in v for name, v in table.items())]
     if missing:
         os.remove(out)
@@ -118,7 +119,7 @@ def kernel_resources(remarks):
 def build_hip_casedump(force=False):
     """Test build of the HIP library that also records the case codes it looks up (tests/test_case_codes.py)."""
     out = os.path.join(CSRC, "libvoxels_hip_casedump.so")
-    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_overlap.inl", "tv_overlap.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_walk.inl", "tv_walk.h", "vx_undo.inl", "tv_undo.h", "vx_stamp.inl", "tv_stamp.h", "vx_lod.inl", "tv_lod.h", "vx_scatter.inl", "tv_scatter.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
+    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_overlap.inl", "tv_overlap.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_walk.inl", "tv_walk.h", "vx_undo.inl", "tv_undo.h", "vx_stamp.inl", "tv_stamp.h", "vx_measure.inl", "tv_measure.h", "vx_lod.inl", "tv_lod.h", "vx_scatter.inl", "tv_scatter.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
     if not force and not _newer(out, srcs):
         return out
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -130,7 +131,7 @@ def build_hip_conservative(force=False):
     """Test build of the HIP library whose in-kernel dependency flags use release / acquire fences instead of write-through
     stores and loads (-DVX_CONSERVATIVE_SYNC, vx_hip.hip): tests/test_gpu_parity.py compares it with the product library."""
     out = os.path.join(CSRC, "libvoxels_hip_conservative.so")
-    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_overlap.inl", "tv_overlap.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_walk.inl", "tv_walk.h", "vx_undo.inl", "tv_undo.h", "vx_stamp.inl", "tv_stamp.h", "vx_lod.inl", "tv_lod.h", "vx_scatter.inl", "tv_scatter.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
+    srcs = [os.path.join(CSRC, f) for f in ("vx_hip.hip", "vx_regular0.inl", "vx_fast0.inl", "vx_fast1.inl", "vx_fastt.inl", "vx_main.inl", "vx_host.inl", "vx_ray.inl", "tv_ray.h", "vx_shape.inl", "tv_shape.h", "vx_overlap.inl", "tv_overlap.h", "vx_brush.inl", "tv_brush.h", "vx_island.inl", "tv_island.h", "vx_smooth.inl", "tv_smooth.h", "vx_walk.inl", "tv_walk.h", "vx_undo.inl", "tv_undo.h", "vx_stamp.inl", "tv_stamp.h", "vx_measure.inl", "tv_measure.h", "vx_lod.inl", "tv_lod.h", "vx_scatter.inl", "tv_scatter.h", "tv_block.h", "tv_core.h", "tv_fast0.h", "tv_fast1.h", "tv_fastt.h", "tv_tables.inc")]
     if not force and not _newer(out, srcs):
         return out
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -284,6 +285,19 @@ def build_stamp_host(force=False):
     if not force and not _newer(out, srcs):
         return out
     subprocess.check_call(["g++", "-std=c++14", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-o", out, os.path.join(d, "stamp_host.cpp")], cwd=d)
+    return out
+
+
+def build_measure_host(force=False):
+    """Host side of the tests of the measurements: csrc/tv_measure.h in a plain triple loop, and the kernels' pipeline (rows, block
+    partials, merges into box results, finish) run on the CPU with the chunk size as a parameter, the entry checks and the layout of
+    the header's structs - tests only (tests/test_measure.py, tests/test_abi_measure.py)."""
+    d = os.path.join(ROOT, "tests", "measure")
+    out = os.path.join(d, "libvoxels_measure_host.so")
+    srcs = [os.path.join(d, "measure_host.cpp"), os.path.join(CSRC, "tv_measure.h"), os.path.join(CSRC, "tv_undo.h"), os.path.join(ROOT, "include", "voxels_hip.h")]
+    if not force and not _newer(out, srcs):
+        return out
+    subprocess.check_call(["g++", "-std=c++14", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-o", out, os.path.join(d, "measure_host.cpp")], cwd=d)
     return out
 
 

@@ -4350,6 +4350,7 @@ struct Backend {
 #include "vx_undo.inl"
 #include "vx_brush.inl"
 #include "vx_stamp.inl"
+#include "vx_measure.inl"
 #include "vx_island.inl"
 #include "vx_smooth.inl"
 #include "vx_walk.inl"

@@ -208,6 +208,9 @@ struct vx_ctx {
 	// stamps (vx_stamp.inl): the stamps the context owns and the device buffers of its paste batches
 	void* stampState = nullptr;
 	void (*stampFree)(vx_ctx*) = nullptr;
+	// measurements (vx_measure.inl): its device buffer and the chunk size of its launches
+	void* measureState = nullptr;
+	void (*measureFree)(vx_ctx*) = nullptr;
 };
 
 // What only a backend with a device clock and a header the host can wait on offers (VX_BACKEND_HEADER_WAIT, defined by the
@@ -951,6 +954,7 @@ void vx_ctx_destroy(vx_ctx* c)
 	if (c->undoFree) c->undoFree(c);
 	if (c->overlapFree) c->overlapFree(c);
 	if (c->stampFree) c->stampFree(c);
+	if (c->measureFree) c->measureFree(c);
 	c->be.shutdown();
 	delete c;
 }
