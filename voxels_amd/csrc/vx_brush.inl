@@ -41,16 +41,12 @@ struct BrushState {
 	size_t bufCap = 0;
 	std::vector<u32> stamp; // host: per block, the last chunk that counted it (distinct blocks of a chunk)
 	u32 stampNow = 0;
-};
 
-void brush_free(vx_ctx* c)
-{
-	BrushState* s = (BrushState*)c->brushState;
-	if (!s) return;
-	c->be.free(s->count); c->be.free(s->slotOf); c->be.free(s->buf);
-	delete s;
-	c->brushState = nullptr;
-}
+	void release(vx_ctx* c)
+	{
+		c->be.free(count); c->be.free(slotOf); c->be.free(buf);
+	}
+};
 
 // The blocks brush b touches, per axis first .. first + cnt - 1: the tests of edit_touched_box (vx_host.inl), which are
 // the reference's expressions; the lanes of a wave take the blocks of an axis 64 at a time.
@@ -325,8 +321,7 @@ int vx_grid_inject_brushes(vx_ctx* c, const vx_brush* brushes, uint32_t count, v
 		if (b.shape == VX_BRUSH_MATERIAL && b.material > 255u) return fail(c, VX_ERR_INVALID, std::string(what) + ": material above 255 in brush " + std::to_string(i));
 	}
 
-	BrushState* s = (BrushState*)c->brushState;
-	if (!s) { s = new BrushState(); c->brushState = s; c->brushFree = brush_free; }
+	BrushState* s = module_state<BrushState>(c, MOD_BRUSH);
 	const u32 nb = c->n / 16;
 	const size_t blocks = (size_t)nb * nb * nb;
 	if (s->stamp.size() != blocks) { s->stamp.assign(blocks, 0); s->stampNow = 0; }

@@ -107,6 +107,18 @@ __device__ __forceinline__ u32 wave_inclusive_scan(u32 v)
 	return v;
 }
 
+// (the 64-bit totals of vx_scatter.inl and vx_overlap.inl)
+__device__ __forceinline__ unsigned long long scatter_wave_scan64(unsigned long long v)
+{
+	const int lane = threadIdx.x & 63;
+#pragma unroll
+	for (int off = 1; off < 64; off <<= 1) {
+		const unsigned long long t = __shfl_up(v, off, 64);
+		if (lane >= off) v += t;
+	}
+	return v;
+}
+
 // in-place exclusive scan of a[0..n) (LDS), all 256 threads must call; returns the total
 __device__ u32 block_exclusive_scan_u16(u16* a, u32 n, u32* scratch)
 {

@@ -47,6 +47,14 @@ typedef ListedBlock EmittedBlock;
 
 // largest grid edge: 2048 = 8 LOD levels (MAX_LEVELS) and 32-bit element offsets inside a block neighbourhood
 enum { VX_MAX_GRID = 2048 };
+// The query and edit modules (vx_<name>.inl), in the order vx_ctx_destroy drops their states.  A slot holds what one module
+// keeps between calls; this file knows no module's type (module_state below).
+enum ModuleId { MOD_RAY, MOD_LOD, MOD_BRUSH, MOD_ISLAND, MOD_SMOOTH, MOD_SCATTER, MOD_WALK, MOD_UNDO, MOD_OVERLAP, MOD_STAMP, MOD_MEASURE, MOD_COUNT };
+struct ModuleSlot {
+	void* state;
+	void (*drop)(vx_ctx*, void*);
+};
+
 enum { HDR_WORDS = 576, HDR_LISTS = 8, HDR_CURSORS = 32, HDR_STATS = 128, HDR_WORK = 160, HDR_LARGE = 176, HDR_SLOW = 224, HDR_UPPER = 256, HDR_GIVEUP = 288, HDR_PUBLISHED = 289 /* workgroups of the list pass that are done; in the host copy: the tag of the run whose header this is */, HDR_L0HEAD = 320 /* the head of k_main's level-0 queue, one for the chip */, HDR_CLOCK0 = 352, HDR_CLOCK1 = 384 /* the 100 MHz clock at the start of k_run_head (of k_main in a run that keeps the slot plan) / at the publication of the header */, HDR_PARTIALS = 32768 }; // counters spread over 128-byte lines
 
 } // namespace
@@ -178,39 +186,10 @@ struct vx_ctx {
 	// the same address, so pointers say nothing); fullRunEpoch = its value after the last full run (the block tables' counts are
 	// then the run's device header words)
 	uint64_t meshEpoch = 0, fullRunEpoch = ~0ull;
-	void* rayState = nullptr;
-	void (*rayFree)(vx_ctx*) = nullptr;
-	// LOD selection (vx_lod.inl): its device buffers, and the first level the last full run meshed (vx_polygonize_from)
-	void* lodState = nullptr;
-	void (*lodFree)(vx_ctx*) = nullptr;
+	// LOD selection (vx_lod.inl): the first level the last full run meshed (vx_polygonize_from)
 	u32 firstMeshedLevel = 0;
-	// brush batches (vx_brush.inl): its device buffers
-	void* brushState = nullptr;
-	void (*brushFree)(vx_ctx*) = nullptr;
-	// detached solid pieces (vx_island.inl): its device buffers
-	void* islandState = nullptr;
-	void (*islandFree)(vx_ctx*) = nullptr;
-	// smoothing (vx_smooth.inl): its device buffers
-	void* smoothState = nullptr;
-	void (*smoothFree)(vx_ctx*) = nullptr;
-	// scattering (vx_scatter.inl): its device buffers
-	void* scatterState = nullptr;
-	void (*scatterFree)(vx_ctx*) = nullptr;
-	// walk fields (vx_walk.inl): its device buffers
-	void* walkState = nullptr;
-	void (*walkFree)(vx_ctx*) = nullptr;
-	// undo records (vx_undo.inl): the records the context owns and its device buffers
-	void* undoState = nullptr;
-	void (*undoFree)(vx_ctx*) = nullptr;
-	// overlap queries (vx_overlap.inl): its device buffers
-	void* overlapState = nullptr;
-	void (*overlapFree)(vx_ctx*) = nullptr;
-	// stamps (vx_stamp.inl): the stamps the context owns and the device buffers of its paste batches
-	void* stampState = nullptr;
-	void (*stampFree)(vx_ctx*) = nullptr;
-	// measurements (vx_measure.inl): its device buffer and the chunk size of its launches
-	void* measureState = nullptr;
-	void (*measureFree)(vx_ctx*) = nullptr;
+	// what the query and edit modules keep between calls (module_state)
+	ModuleSlot modules[MOD_COUNT] = {};
 };
 
 // What only a backend with a device clock and a header the host can wait on offers (VX_BACKEND_HEADER_WAIT, defined by the
@@ -256,6 +235,45 @@ int fail(vx_ctx* c, int code, const std::string& msg)
 {
 	if (c) c->err = msg;
 	return code;
+}
+
+// A module's state S (default-constructible, with `void release(vx_ctx*)` that frees what it holds): created on first use and
+// dropped - release, then delete - by vx_ctx_destroy.  `setup`: run once on the new state; where it fails the state is dropped
+// again and the caller gets null.
+template <class S> S* module_peek(const vx_ctx* c, ModuleId id) { return (S*)c->modules[id].state; } // null: not created yet
+
+void module_drop(vx_ctx* c, ModuleId id)
+{
+	ModuleSlot& m = c->modules[id];
+	if (m.state) m.drop(c, m.state);
+	m.state = nullptr;
+	m.drop = nullptr;
+}
+
+template <class S> S* module_state(vx_ctx* c, ModuleId id, bool (S::*setup)(vx_ctx*) = nullptr)
+{
+	ModuleSlot& m = c->modules[id];
+	if (m.state) return (S*)m.state;
+	S* s = new S();
+	m.state = s;
+	m.drop = [](vx_ctx* ctx, void* p) { S* st = (S*)p; st->release(ctx); delete st; };
+	if (setup && !(s->*setup)(c)) {
+		module_drop(c, id);
+		return nullptr;
+	}
+	return s;
+}
+
+// device buffer of at least `bytes` (contents not kept)
+template <typename T>
+bool dev_grow(vx_ctx* c, T*& p, size_t& cap, size_t bytes)
+{
+	if (bytes <= cap && p) return true;
+	c->be.free(p);
+	cap = bytes + bytes / 4 + 256;
+	p = (T*)c->be.alloc(cap);
+	if (!p) cap = 0;
+	return p != nullptr;
 }
 
 u32 ref_levels(u32 n)
@@ -944,17 +962,7 @@ void vx_ctx_destroy(vx_ctx* c)
 	c->be.comm_destroy();
 	c->be.free_pinned(c->hdrPinned);
 	c->be.free(c->dScratch);
-	if (c->rayFree) c->rayFree(c);
-	if (c->lodFree) c->lodFree(c);
-	if (c->brushFree) c->brushFree(c);
-	if (c->islandFree) c->islandFree(c);
-	if (c->smoothFree) c->smoothFree(c);
-	if (c->scatterFree) c->scatterFree(c);
-	if (c->walkFree) c->walkFree(c);
-	if (c->undoFree) c->undoFree(c);
-	if (c->overlapFree) c->overlapFree(c);
-	if (c->stampFree) c->stampFree(c);
-	if (c->measureFree) c->measureFree(c);
+	for (int id = 0; id < MOD_COUNT; ++id) module_drop(c, (ModuleId)id);
 	c->be.shutdown();
 	delete c;
 }

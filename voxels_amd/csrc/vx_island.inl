@@ -52,18 +52,14 @@ struct IslState {
 	void* touched = nullptr;  // ids of the blocks a removal rewrote (one per tile at most)
 	size_t touchedCap = 0;
 	void* small = nullptr;    // IslCounts, the dirty box, the list total
+
+	void release(vx_ctx* c)
+	{
+		c->be.free(volume); c->be.free(rows); c->be.free(perRecord); c->be.free(touched); c->be.free(small);
+	}
 };
 
 enum { ISL_SMALL_BYTES = 256, ISL_AT_DIRTY = 64, ISL_AT_LISTED = 96 };
-
-void island_free(vx_ctx* c)
-{
-	IslState* s = (IslState*)c->islandState;
-	if (!s) return;
-	c->be.free(s->volume); c->be.free(s->rows); c->be.free(s->perRecord); c->be.free(s->touched); c->be.free(s->small);
-	delete s;
-	c->islandState = nullptr;
-}
 
 __global__ __launch_bounds__(WG) void k_isl_local(GridView g, const u8* flags, IslRegion r, u32* L)
 {
@@ -218,16 +214,6 @@ __global__ __launch_bounds__(WG) void k_isl_remove(GridView g, IslRegion r, cons
 	if (t == 0 && any) { const u32 slot = atomicAdd(&counts->touched_blocks, 1u); if (slot < touchedCap) touched[slot] = T.block; }
 }
 
-bool island_grow(vx_ctx* c, void*& p, size_t& cap, size_t need)
-{
-	if (need <= cap) return true;
-	c->be.free(p);
-	cap = need + need / 4;
-	p = c->be.alloc(cap);
-	if (!p) { cap = 0; return false; }
-	return true;
-}
-
 } // namespace
 
 extern "C" {
@@ -262,15 +248,14 @@ int vx_grid_islands(vx_ctx* c, const vx_island_query* q, vx_island* islands, uin
 	}
 	if (V > (1ull << 30)) return fail(c, VX_ERR_INVALID, std::string(what) + ": the box holds more than 2^30 voxels");
 
-	IslState* s = (IslState*)c->islandState;
-	if (!s) { s = new IslState(); c->islandState = s; c->islandFree = island_free; }
+	IslState* s = module_state<IslState>(c, MOD_ISLAND);
 	const IslRegion r = isl_region(c->n, lo, hi);
 	const u32 tiles = isl_tiles(r), rows = isl_rows(r);
 	auto noMemory = [&]() { return fail(c, VX_ERR_DEVICE, std::string(what) + ": allocation failed: " + c->be.error()); };
 	if (!s->small && !(s->small = c->be.alloc(ISL_SMALL_BYTES))) return noMemory();
-	if (!d_labels && !island_grow(c, s->volume, s->volumeCap, (size_t)V * 4)) return noMemory();
-	if (!island_grow(c, s->rows, s->rowsCap, ((size_t)rows + 1) * 4)) return noMemory();
-	if (remove && !island_grow(c, s->touched, s->touchedCap, (size_t)tiles * 4)) return noMemory();
+	if (!d_labels && !dev_grow(c, s->volume, s->volumeCap, (size_t)V * 4)) return noMemory();
+	if (!dev_grow(c, s->rows, s->rowsCap, ((size_t)rows + 1) * 4)) return noMemory();
+	if (remove && !dev_grow(c, s->touched, s->touchedCap, (size_t)tiles * 4)) return noMemory();
 
 	u32* L = d_labels ? d_labels : (u32*)s->volume;
 	u32* rowOff = (u32*)s->rows;
@@ -301,7 +286,7 @@ int vx_grid_islands(vx_ctx* c, const vx_island_query* q, vx_island* islands, uin
 		auto pad = [](size_t v) { return (v + 255) & ~(size_t)255; };
 		const size_t atRoots = 0, atRecs = pad((size_t)comps * 4), atMarks = atRecs + pad((size_t)comps * sizeof(IslRecord));
 		const size_t atList = atMarks + pad(comps), atOut = atList + pad((size_t)comps * 4), need = atOut + pad((size_t)outCap * sizeof(IslRecord));
-		if (!island_grow(c, s->perRecord, s->perRecordCap, need)) return noMemory();
+		if (!dev_grow(c, s->perRecord, s->perRecordCap, need)) return noMemory();
 		char* base = (char*)s->perRecord;
 		u32* roots = (u32*)(base + atRoots);
 		IslRecord* recs = (IslRecord*)(base + atRecs);

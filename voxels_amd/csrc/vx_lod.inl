@@ -298,25 +298,12 @@ struct LodState {
 	size_t wgSumsCap = 0;       // bytes
 	void* io = nullptr;         // vx_lod_select: the output arrays on their way to the host
 	size_t ioCap = 0;
-};
 
-void lod_free(vx_ctx* c)
-{
-	LodState* s = (LodState*)c->lodState;
-	if (!s) return;
-	c->be.free(s->open); c->be.free(s->partials); c->be.free(s->words); c->be.free(s->wgSums); c->be.free(s->io);
-	delete s;
-	c->lodState = nullptr;
-}
-
-LodState* lod_state(vx_ctx* c)
-{
-	if (!c->lodState) {
-		c->lodState = new LodState;
-		c->lodFree = lod_free;
+	void release(vx_ctx* c)
+	{
+		c->be.free(open); c->be.free(partials); c->be.free(words); c->be.free(wgSums); c->be.free(io);
 	}
-	return (LodState*)c->lodState;
-}
+};
 
 bool lod_nan(float v) { return v != v; }
 
@@ -341,7 +328,7 @@ int lod_check(vx_ctx* c, const vx_lod_params* prm, uint32_t drawCap, uint32_t tr
 int lod_launch(vx_ctx* c, const vx_lod_params* prm, uint32_t drawCap, uint32_t trCap, vx_lod_draw* dDraws,
                vx_draw_indexed* dRegular, vx_draw_indexed* dTransition, vx_lod_counts* dCounts, const char* what)
 {
-	LodState* s = lod_state(c);
+	LodState* s = module_state<LodState>(c, MOD_LOD);
 	const u32 T = c->levelsRun - 1;
 	LodEmitParams e;
 	memset(&e, 0, sizeof(e));
@@ -360,7 +347,7 @@ int lod_launch(vx_ctx* c, const vx_lod_params* prm, uint32_t drawCap, uint32_t t
 	}
 	lp.base[T + 1] = (u32)nodes;
 	const u32 wgs = (u32)((nodes + WG - 1) / WG);
-	if (!ray_grow(c, s->open, s->openCap, flagBytes) || !ray_grow(c, s->partials, s->partialsCap, (size_t)wgs * 16))
+	if (!dev_grow(c, s->open, s->openCap, flagBytes) || !dev_grow(c, s->partials, s->partialsCap, (size_t)wgs * 16))
 		return fail(c, VX_ERR_DEVICE, std::string(what) + ": allocation failed: " + c->be.error());
 	for (u32 L = 1; L <= T; ++L) p.open[L] = s->open + flagOff[L];
 	p.T = T;
@@ -383,7 +370,7 @@ int lod_launch(vx_ctx* c, const vx_lod_params* prm, uint32_t drawCap, uint32_t t
 	e.base[T + 1] = width;
 	const u32 nWg = (width + WG - 1) / WG;
 	const size_t wgCap = (entryCap + WG - 1) / WG + 1;
-	if (!ray_grow(c, s->words, s->wordsCap, entryCap * 4) || !ray_grow(c, s->wgSums, s->wgSumsCap, wgCap * 24))
+	if (!dev_grow(c, s->words, s->wordsCap, entryCap * 4) || !dev_grow(c, s->wgSums, s->wgSumsCap, wgCap * 24))
 		return fail(c, VX_ERR_DEVICE, std::string(what) + ": allocation failed: " + c->be.error());
 	e.words = s->words;
 	e.wgTotals = (uint4*)s->wgSums;
@@ -453,10 +440,10 @@ int vx_lod_select(vx_ctx* c, const vx_lod_params* prm, uint32_t draw_capacity, u
 	VX_ENTER(c);
 	int rc = lod_check(c, prm, draw_capacity, transition_capacity, draws, regular, transition, counts, "vx_lod_select");
 	if (rc != VX_OK) return rc;
-	LodState* s = lod_state(c);
+	LodState* s = module_state<LodState>(c, MOD_LOD);
 	const size_t drawBytes = (size_t)draw_capacity * sizeof(vx_lod_draw), regBytes = lod_align16((size_t)draw_capacity * sizeof(vx_draw_indexed));
 	const size_t trBytes = lod_align16((size_t)transition_capacity * sizeof(vx_draw_indexed));
-	if (!ray_grow(c, s->io, s->ioCap, sizeof(vx_lod_counts) + drawBytes + regBytes + trBytes))
+	if (!dev_grow(c, s->io, s->ioCap, sizeof(vx_lod_counts) + drawBytes + regBytes + trBytes))
 		return fail(c, VX_ERR_DEVICE, "vx_lod_select: allocation failed: " + c->be.error());
 	char* io = (char*)s->io;
 	vx_lod_counts* dCounts = (vx_lod_counts*)io;

@@ -24,32 +24,12 @@ struct MeasureState {
 	size_t bufCap = 0;
 	u64 chunk = MEASURE_CHUNK_PAIRS;
 	bool shortcuts = true;     // the sign summaries may stand in for the distance rows (vx_debug_measure_shortcuts)
+
+	void release(vx_ctx* c)
+	{
+		c->be.free(buf);
+	}
 };
-
-void measure_state_free(vx_ctx* c)
-{
-	MeasureState* s = (MeasureState*)c->measureState;
-	if (!s) return;
-	c->be.free(s->buf);
-	delete s;
-	c->measureState = nullptr;
-}
-
-MeasureState* measure_state(vx_ctx* c)
-{
-	if (!c->measureState) { c->measureState = new MeasureState(); c->measureFree = measure_state_free; }
-	return (MeasureState*)c->measureState;
-}
-
-bool measure_grow(vx_ctx* c, MeasureState* s, size_t need)
-{
-	if (need <= s->bufCap) return true;
-	c->be.free(s->buf);
-	s->bufCap = need + need / 4;
-	s->buf = c->be.alloc(s->bufCap);
-	if (!s->buf) { s->bufCap = 0; return false; }
-	return true;
-}
 
 // The sign summaries (MirrorState::blockSign, field 0: 1 = every sample of the block is >= 0, 2 = every sample is < 0) describe
 // the dense fields while the mirrors are current: every device edit brings them up to date over the blocks it touched
@@ -212,14 +192,14 @@ static_assert(VX_MEASURE_MAX_BOXES == tv::MEASURE_MAX_BOXES, "measurement limits
 int vx_debug_measure_chunk(vx_ctx* c, uint32_t pairs)
 {
 	if (!c) return VX_ERR_INVALID;
-	measure_state(c)->chunk = pairs ? std::min<u64>(pairs, 1u << 30) : (u64)MEASURE_CHUNK_PAIRS; // (a launch's workgroup count has a limit of its own)
+	module_state<MeasureState>(c, MOD_MEASURE)->chunk = pairs ? std::min<u64>(pairs, 1u << 30) : (u64)MEASURE_CHUNK_PAIRS; // (a launch's workgroup count has a limit of its own)
 	return VX_OK;
 }
 
 int vx_debug_measure_shortcuts(vx_ctx* c, uint32_t enable)
 {
 	if (!c) return VX_ERR_INVALID;
-	measure_state(c)->shortcuts = enable != 0;
+	module_state<MeasureState>(c, MOD_MEASURE)->shortcuts = enable != 0;
 	return VX_OK;
 }
 
@@ -232,7 +212,7 @@ int vx_grid_measure(vx_ctx* c, const vx_box* boxes, uint32_t count, vx_measure* 
 	if (const char* bad = measure_check(c->n, (const RecBox*)boxes, count, results)) return fail(c, VX_ERR_INVALID, what + bad);
 	if (!count) return VX_OK;
 
-	MeasureState* s = measure_state(c);
+	MeasureState* s = module_state<MeasureState>(c, MOD_MEASURE);
 	std::vector<u64> prefix((size_t)count + 1u);
 	prefix[0] = 0;
 	for (u32 i = 0; i < count; ++i) prefix[i + 1u] = prefix[i] + measure_box_pairs(((const RecBox*)boxes)[i]);
@@ -243,7 +223,7 @@ int vx_grid_measure(vx_ctx* c, const vx_box* boxes, uint32_t count, vx_measure* 
 	const size_t atBoxes = 0, atPrefix = pad((size_t)count * sizeof(RecBox)), atSlots = atPrefix + pad(((size_t)count + 1u) * 8u);
 	const size_t atTallies = atSlots + pad((size_t)count * sizeof(MeasureSlot)), atResults = atTallies + (size_t)count * 2048u;
 	const size_t need = atResults + (size_t)count * sizeof(MeasureResult);
-	if (!measure_grow(c, s, need)) return fail(c, VX_ERR_DEVICE, what + "allocation failed: " + c->be.error());
+	if (!dev_grow(c, s->buf, s->bufCap, need)) return fail(c, VX_ERR_DEVICE, what + "allocation failed: " + c->be.error());
 	char* base = (char*)s->buf;
 	const RecBox* dBoxes = (const RecBox*)(base + atBoxes);
 	const u64* dPrefix = (const u64*)(base + atPrefix);
@@ -282,9 +262,9 @@ int vx_record_measure(vx_ctx* c, const vx_record* r, vx_record_delta* delta, uin
 	if (added) memset(added, 0, 2048);
 	if (!r->blocks) return VX_OK;
 
-	MeasureState* s = measure_state(c);
+	MeasureState* s = module_state<MeasureState>(c, MOD_MEASURE);
 	const size_t atTallies = 256, bytes = atTallies + 4096u;   // the slot | removed, added
-	if (!measure_grow(c, s, bytes)) return fail(c, VX_ERR_DEVICE, what + "allocation failed: " + c->be.error());
+	if (!dev_grow(c, s->buf, s->bufCap, bytes)) return fail(c, VX_ERR_DEVICE, what + "allocation failed: " + c->be.error());
 	char* base = (char*)s->buf;
 	bool ok = c->be.fill(base, 0, bytes);
 	if (ok) {

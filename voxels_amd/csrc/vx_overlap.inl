@@ -241,25 +241,12 @@ struct OverlapState {
 	size_t perCap = 0;          // bytes
 	void* io = nullptr;         // vx_overlap_boxes: the boxes and the output arrays on their way through the device
 	size_t ioCap = 0;
-};
 
-void overlap_free(vx_ctx* c)
-{
-	OverlapState* s = (OverlapState*)c->overlapState;
-	if (!s) return;
-	c->be.free(s->per); c->be.free(s->io);
-	delete s;
-	c->overlapState = nullptr;
-}
-
-OverlapState* overlap_state(vx_ctx* c)
-{
-	if (!c->overlapState) {
-		c->overlapState = new OverlapState;
-		c->overlapFree = overlap_free;
+	void release(vx_ctx* c)
+	{
+		c->be.free(per); c->be.free(io);
 	}
-	return (OverlapState*)c->overlapState;
-}
+};
 
 int overlap_check(vx_ctx* c, uint32_t level, const void* boxes, uint32_t n, uint32_t capacity, const void* tris, const void* corners,
                   const void* counts, const char* what)
@@ -280,12 +267,12 @@ int overlap_check(vx_ctx* c, uint32_t level, const void* boxes, uint32_t n, uint
 int overlap_launch(vx_ctx* c, uint32_t level, const vx_overlap_box* dBoxes, uint32_t n, uint32_t capacity, vx_overlap_tri* dTris,
                    float* dCorners, vx_overlap_range* dRanges, vx_overlap_counts* dCounts, const char* what)
 {
-	OverlapState* s = overlap_state(c);
+	OverlapState* s = module_state<OverlapState>(c, MOD_OVERLAP);
 	int rc = ray_prepare(c, level);
 	if (rc != VX_OK) return rc;
-	if (n && !ray_grow(c, s->per, s->perCap, (size_t)n * sizeof(OverlapQuery)))
+	if (n && !dev_grow(c, s->per, s->perCap, (size_t)n * sizeof(OverlapQuery)))
 		return fail(c, VX_ERR_DEVICE, std::string(what) + ": allocation failed: " + c->be.error());
-	const RayState* rs = (const RayState*)c->rayState;
+	const RayState* rs = module_peek<RayState>(c, MOD_RAY);
 	const RayLevel& l = rs->lv[level];
 	OverlapParams p;
 	memset(&p, 0, sizeof(p));
@@ -349,10 +336,10 @@ int vx_overlap_boxes(vx_ctx* c, uint32_t level, const vx_overlap_box* boxes, uin
 	VX_ENTER(c);
 	int rc = overlap_check(c, level, boxes, n, capacity, tris, corners, counts, "vx_overlap_boxes");
 	if (rc != VX_OK) return rc;
-	OverlapState* s = overlap_state(c);
+	OverlapState* s = module_state<OverlapState>(c, MOD_OVERLAP);
 	const size_t boxBytes = (size_t)n * sizeof(vx_overlap_box), rangeBytes = lod_align16((size_t)n * sizeof(vx_overlap_range));
 	const size_t triBytes = (size_t)capacity * sizeof(vx_overlap_tri), cornerBytes = corners ? (size_t)capacity * 48u : 0u;
-	if (!ray_grow(c, s->io, s->ioCap, sizeof(vx_overlap_counts) + boxBytes + rangeBytes + triBytes + cornerBytes))
+	if (!dev_grow(c, s->io, s->ioCap, sizeof(vx_overlap_counts) + boxBytes + rangeBytes + triBytes + cornerBytes))
 		return fail(c, VX_ERR_DEVICE, "vx_overlap_boxes: allocation failed: " + c->be.error());
 	char* io = (char*)s->io;   // (every part is a multiple of 16 bytes)
 	vx_overlap_counts* dCounts = (vx_overlap_counts*)io;

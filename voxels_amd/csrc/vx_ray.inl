@@ -233,47 +233,22 @@ struct RayState {
 	void* io = nullptr;         // vx_raycast: rays and hits on their way through the device
 	size_t ioCap = 0;
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
-};
 
-void ray_free(vx_ctx* c)
-{
-	RayState* s = (RayState*)c->rayState;
-	if (!s) return;
-	for (RayLevel& l : s->lv) { c->be.free(l.map); c->be.free(l.starts); }
-	c->be.free(s->perm); c->be.free(s->stats); c->be.free(s->io);
-	c->be.free_pinned(s->statsHost);
-	if (s->ev0) (void)hipEventDestroy(s->ev0);
-	if (s->ev1) (void)hipEventDestroy(s->ev1);
-	delete s;
-	c->rayState = nullptr;
-}
-
-RayState* ray_state(vx_ctx* c)
-{
-	if (c->rayState) return (RayState*)c->rayState;
-	RayState* s = new RayState;
-	c->rayState = s;
-	c->rayFree = ray_free;
-	s->stats = (unsigned long long*)c->be.alloc(16);
-	s->statsHost = (unsigned long long*)c->be.alloc_pinned(16);
-	if (!s->stats || !s->statsHost || !c->be.check(hipEventCreate(&s->ev0), "hipEventCreate") || !c->be.check(hipEventCreate(&s->ev1), "hipEventCreate")) {
-		ray_free(c);
-		return nullptr;
+	bool setup(vx_ctx* c)
+	{
+		stats = (unsigned long long*)c->be.alloc(16);
+		statsHost = (unsigned long long*)c->be.alloc_pinned(16);
+		return stats && statsHost && c->be.check(hipEventCreate(&ev0), "hipEventCreate") && c->be.check(hipEventCreate(&ev1), "hipEventCreate");
 	}
-	return s;
-}
-
-// device buffer of at least `bytes` (contents not kept)
-template <typename T>
-bool ray_grow(vx_ctx* c, T*& p, size_t& cap, size_t bytes)
-{
-	if (bytes <= cap && p) return true;
-	c->be.free(p);
-	cap = bytes + bytes / 4 + 256;
-	p = (T*)c->be.alloc(cap);
-	if (!p) cap = 0;
-	return p != nullptr;
-}
+	void release(vx_ctx* c)
+	{
+		for (RayLevel& l : lv) { c->be.free(l.map); c->be.free(l.starts); }
+		c->be.free(perm); c->be.free(stats); c->be.free(io);
+		c->be.free_pinned(statsHost);
+		if (ev0) (void)hipEventDestroy(ev0);
+		if (ev1) (void)hipEventDestroy(ev1);
+	}
+};
 
 int ray_check(vx_ctx* c, uint32_t level, const char* what)
 {
@@ -285,14 +260,14 @@ int ray_check(vx_ctx* c, uint32_t level, const char* what)
 
 bool ray_current(vx_ctx* c, uint32_t level)
 {
-	const RayState* s = (const RayState*)c->rayState;
+	const RayState* s = module_peek<RayState>(c, MOD_RAY);
 	return s && s->lv[level].built && s->lv[level].epoch == c->meshEpoch;
 }
 
 int ray_prepare(vx_ctx* c, uint32_t level)
 {
 	if (ray_current(c, level)) return VX_OK;
-	RayState* s = ray_state(c);
+	RayState* s = module_state<RayState>(c, MOD_RAY, &RayState::setup);
 	if (!s) return fail(c, VX_ERR_DEVICE, "vx_raycast_prepare: allocation failed: " + c->be.error());
 	const vx_listed_block* tab = nullptr;
 	u32 nb = 0;
@@ -305,9 +280,9 @@ int ray_prepare(vx_ctx* c, uint32_t level)
 	const size_t permBytes = ((size_t)c->poolIdx / 3 + 1) * 2;
 	if (permBytes > s->permCap || !s->perm) {
 		for (RayLevel& o : s->lv) o.built = false; // (the other levels' parts of the permutation are gone)
-		if (!ray_grow(c, s->perm, s->permCap, permBytes)) return fail(c, VX_ERR_DEVICE, "vx_raycast_prepare: allocation failed: " + c->be.error());
+		if (!dev_grow(c, s->perm, s->permCap, permBytes)) return fail(c, VX_ERR_DEVICE, "vx_raycast_prepare: allocation failed: " + c->be.error());
 	}
-	if (!ray_grow(c, l.map, l.mapCap, mapBytes) || !ray_grow(c, l.starts, l.startsCap, startsBytes))
+	if (!dev_grow(c, l.map, l.mapCap, mapBytes) || !dev_grow(c, l.starts, l.startsCap, startsBytes))
 		return fail(c, VX_ERR_DEVICE, "vx_raycast_prepare: allocation failed: " + c->be.error());
 	RayIndexParams p;
 	p.table = (const ListedBlock*)tab;
@@ -345,7 +320,7 @@ int ray_prepare(vx_ctx* c, uint32_t level)
 
 int ray_launch(vx_ctx* c, uint32_t level, const vx_ray* dRays, uint32_t n, vx_ray_hit* dHits)
 {
-	const RayState* s = (const RayState*)c->rayState;
+	const RayState* s = module_peek<RayState>(c, MOD_RAY);
 	const RayLevel& l = s->lv[level];
 	RayCastParams p;
 	p.rays = (const float4*)dRays;
@@ -374,7 +349,7 @@ int vx_raycast_prepare(vx_ctx* c, uint32_t level, vx_ray_index_info* info)
 	VX_ENTER(c);
 	int rc = ray_check(c, level, "vx_raycast_prepare");
 	if (rc == VX_OK) rc = ray_prepare(c, level);
-	if (rc == VX_OK && info) *info = ((const RayState*)c->rayState)->lv[level].info;
+	if (rc == VX_OK && info) *info = module_peek<RayState>(c, MOD_RAY)->lv[level].info;
 	return rc;
 }
 
@@ -398,9 +373,9 @@ int vx_raycast(vx_ctx* c, uint32_t level, const vx_ray* rays, uint32_t n, vx_ray
 	if (n && (!rays || !hits)) return fail(c, VX_ERR_INVALID, "vx_raycast: null array");
 	if (!n) return VX_OK;
 	if ((rc = ray_prepare(c, level)) != VX_OK) return rc;
-	RayState* s = (RayState*)c->rayState;
+	RayState* s = module_peek<RayState>(c, MOD_RAY);
 	const size_t rayBytes = (size_t)n * sizeof(vx_ray), hitBytes = (size_t)n * sizeof(vx_ray_hit);
-	if (!ray_grow(c, s->io, s->ioCap, rayBytes + hitBytes)) return fail(c, VX_ERR_DEVICE, "vx_raycast: allocation failed: " + c->be.error());
+	if (!dev_grow(c, s->io, s->ioCap, rayBytes + hitBytes)) return fail(c, VX_ERR_DEVICE, "vx_raycast: allocation failed: " + c->be.error());
 	vx_ray* dRays = (vx_ray*)s->io;
 	vx_ray_hit* dHits = (vx_ray_hit*)((char*)s->io + rayBytes);
 	if (!c->be.h2d(dRays, rays, rayBytes)) return fail(c, VX_ERR_DEVICE, "vx_raycast: upload failed: " + c->be.error());

@@ -149,17 +149,6 @@ template <bool WRITE> __device__ __forceinline__ void scatter_entry(const Scatte
 __global__ __launch_bounds__(WG) void k_scatter_count(ScatterParams p) { scatter_entry<false>(p); }
 __global__ __launch_bounds__(WG) void k_scatter_write(ScatterParams p) { scatter_entry<true>(p); }
 
-__device__ __forceinline__ unsigned long long scatter_wave_scan64(unsigned long long v)
-{
-	const int lane = threadIdx.x & 63;
-#pragma unroll
-	for (int off = 1; off < 64; off <<= 1) {
-		const unsigned long long t = __shfl_up(v, off, 64);
-		if (lane >= off) v += t;
-	}
-	return v;
-}
-
 // one workgroup: the first point of every entry (exclusive scan of the kept counts), the counts, the ranges
 __global__ __launch_bounds__(LOD_SCAN_WG) void k_scatter_scan(ScatterParams p)
 {
@@ -211,25 +200,12 @@ struct ScatterState {
 	size_t totalsCap = 0;       // bytes
 	void* io = nullptr;         // vx_scatter: the output arrays on their way to the host
 	size_t ioCap = 0;
-};
 
-void scatter_free(vx_ctx* c)
-{
-	ScatterState* s = (ScatterState*)c->scatterState;
-	if (!s) return;
-	c->be.free(s->totals); c->be.free(s->io);
-	delete s;
-	c->scatterState = nullptr;
-}
-
-ScatterState* scatter_state(vx_ctx* c)
-{
-	if (!c->scatterState) {
-		c->scatterState = new ScatterState;
-		c->scatterFree = scatter_free;
+	void release(vx_ctx* c)
+	{
+		c->be.free(totals); c->be.free(io);
 	}
-	return (ScatterState*)c->scatterState;
-}
+};
 
 int scatter_check(vx_ctx* c, uint32_t level, const vx_scatter_params* prm, uint32_t capacity, const void* points, const void* counts, const char* what)
 {
@@ -254,14 +230,14 @@ int scatter_check(vx_ctx* c, uint32_t level, const vx_scatter_params* prm, uint3
 int scatter_launch(vx_ctx* c, uint32_t level, const vx_scatter_params* prm, uint32_t capacity, vx_scatter_point* dPoints,
                    vx_scatter_range* dRanges, vx_scatter_counts* dCounts, const char* what)
 {
-	ScatterState* s = scatter_state(c);
+	ScatterState* s = module_state<ScatterState>(c, MOD_SCATTER);
 	const vx_listed_block* tab = nullptr;
 	u32 nb = 0;
 	const int rc = vx_device_block_table(c, level, &tab, &nb);
 	if (rc != VX_OK) return rc;
 	size_t entryCap = nb; // (sized for the levels' table capacities: allocated once per grid)
 	for (u32 L = 0; L < c->levelsRun; ++L) entryCap = std::max<size_t>(entryCap, c->lv[L].cap);
-	if (!ray_grow(c, s->totals, s->totalsCap, entryCap * sizeof(ScatterTotal)))
+	if (!dev_grow(c, s->totals, s->totalsCap, entryCap * sizeof(ScatterTotal)))
 		return fail(c, VX_ERR_DEVICE, std::string(what) + ": allocation failed: " + c->be.error());
 	ScatterParams p;
 	memset(&p, 0, sizeof(p));
@@ -319,12 +295,12 @@ int vx_scatter(vx_ctx* c, uint32_t level, const vx_scatter_params* prm, uint32_t
 	VX_ENTER(c);
 	int rc = scatter_check(c, level, prm, capacity, points, counts, "vx_scatter");
 	if (rc != VX_OK) return rc;
-	ScatterState* s = scatter_state(c);
+	ScatterState* s = module_state<ScatterState>(c, MOD_SCATTER);
 	const vx_listed_block* tab = nullptr;
 	u32 nb = 0;
 	if ((rc = vx_device_block_table(c, level, &tab, &nb)) != VX_OK) return rc;
 	const size_t rangeBytes = lod_align16((size_t)nb * sizeof(vx_scatter_range)), pointBytes = (size_t)capacity * sizeof(vx_scatter_point);
-	if (!ray_grow(c, s->io, s->ioCap, sizeof(vx_scatter_counts) + rangeBytes + pointBytes))
+	if (!dev_grow(c, s->io, s->ioCap, sizeof(vx_scatter_counts) + rangeBytes + pointBytes))
 		return fail(c, VX_ERR_DEVICE, "vx_scatter: allocation failed: " + c->be.error());
 	char* io = (char*)s->io;
 	vx_scatter_counts* dCounts = (vx_scatter_counts*)io;

@@ -291,7 +291,7 @@ __global__ __launch_bounds__(WG) void k_closest_point(ShapeParams p)
 
 ShapeParams shape_params(vx_ctx* c, uint32_t level, const void* in, uint32_t n, void* out)
 {
-	const RayState* s = (const RayState*)c->rayState;
+	const RayState* s = module_peek<RayState>(c, MOD_RAY);
 	const RayLevel& l = s->lv[level];
 	ShapeParams p;
 	p.in = (const float4*)in;
@@ -335,9 +335,9 @@ int shape_host(vx_ctx* c, uint32_t level, bool sphere, const void* in, size_t in
 	if (n && (!in || !out)) return fail(c, VX_ERR_INVALID, std::string(what) + ": null array");
 	if (!n) return VX_OK;
 	if ((rc = ray_prepare(c, level)) != VX_OK) return rc;
-	RayState* s = (RayState*)c->rayState;
+	RayState* s = module_peek<RayState>(c, MOD_RAY);
 	const size_t inBytes = (size_t)n * inSize, outBytes = (size_t)n * outSize;
-	if (!ray_grow(c, s->io, s->ioCap, inBytes + outBytes)) return fail(c, VX_ERR_DEVICE, std::string(what) + ": allocation failed: " + c->be.error());
+	if (!dev_grow(c, s->io, s->ioCap, inBytes + outBytes)) return fail(c, VX_ERR_DEVICE, std::string(what) + ": allocation failed: " + c->be.error());
 	void* dIn = s->io;
 	void* dOut = (char*)s->io + inBytes;   // (inBytes is a multiple of 16)
 	if (!c->be.h2d(dIn, in, inBytes)) return fail(c, VX_ERR_DEVICE, std::string(what) + ": upload failed: " + c->be.error());

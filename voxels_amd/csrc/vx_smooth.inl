@@ -24,18 +24,14 @@ struct SmoothState {
 	size_t idsCap = 0;
 	void* perOp = nullptr;     // slots, then the result records and the union
 	size_t perOpCap = 0;
+
+	void release(vx_ctx* c)
+	{
+		c->be.free(volume); c->be.free(original); c->be.free(ids); c->be.free(perOp);
+	}
 };
 
 struct SmoothParams { float center[3], radius, strength; };
-
-void smooth_free(vx_ctx* c)
-{
-	SmoothState* s = (SmoothState*)c->smoothState;
-	if (!s) return;
-	c->be.free(s->volume); c->be.free(s->original); c->be.free(s->ids); c->be.free(s->perOp);
-	delete s;
-	c->smoothState = nullptr;
-}
 
 __global__ __launch_bounds__(WG) void k_smooth_eval(GridView g, SmoothRegion r, SmoothParams p, i8* volume)
 {
@@ -106,16 +102,6 @@ __global__ __launch_bounds__(WG) void k_smooth_results(const SmoothSlot* slots, 
 	if (t == 0) out[count] = smooth_result(n, all);
 }
 
-bool smooth_grow(vx_ctx* c, void*& p, size_t& cap, size_t need)
-{
-	if (need <= cap) return true;
-	c->be.free(p);
-	cap = need + need / 4;
-	p = c->be.alloc(cap);
-	if (!p) { cap = 0; return false; }
-	return true;
-}
-
 } // namespace
 
 extern "C" {
@@ -156,11 +142,10 @@ int vx_grid_smooth(vx_ctx* c, const vx_smooth* ops, uint32_t count, vx_smooth_re
 	if (results) memset(results, 0, (size_t)count * sizeof(vx_smooth_result));
 	if (!anyActive) return VX_OK;
 
-	SmoothState* s = (SmoothState*)c->smoothState;
-	if (!s) { s = new SmoothState(); c->smoothState = s; c->smoothFree = smooth_free; }
+	SmoothState* s = module_state<SmoothState>(c, MOD_SMOOTH);
 	const size_t atResults = (size_t)count * sizeof(SmoothSlot);
-	if (!smooth_grow(c, s->volume, s->volumeCap, maxTiles * 4096) || (anyOriginal && !smooth_grow(c, s->original, s->originalCap, maxTiles * 4096))
-	    || !smooth_grow(c, s->ids, s->idsCap, maxTiles * 4) || !smooth_grow(c, s->perOp, s->perOpCap, atResults + ((size_t)count + 1) * sizeof(SmoothResult)))
+	if (!dev_grow(c, s->volume, s->volumeCap, maxTiles * 4096) || (anyOriginal && !dev_grow(c, s->original, s->originalCap, maxTiles * 4096))
+	    || !dev_grow(c, s->ids, s->idsCap, maxTiles * 4) || !dev_grow(c, s->perOp, s->perOpCap, atResults + ((size_t)count + 1) * sizeof(SmoothResult)))
 		return fail(c, VX_ERR_DEVICE, std::string(what) + ": allocation failed: " + c->be.error());
 
 	SmoothSlot* slots = (SmoothSlot*)s->perOp;

@@ -40,27 +40,17 @@ struct StampState {
 	void* slot = nullptr;      // RecSwapSlot
 	size_t listCap = BRUSH_LIST_CAP;
 	PastePlan plan;            // host: kept, so that a small batch on a large grid does not pay for every block of the grid
+
+	void release(vx_ctx* c)
+	{
+		for (vx_stamp* st : stamps) { c->be.free(st->mem); delete st; }
+		c->be.free(count); c->be.free(slotOf); c->be.free(buf); c->be.free(slot);
+	}
 };
-
-void stamp_state_free(vx_ctx* c)
-{
-	StampState* s = (StampState*)c->stampState;
-	if (!s) return;
-	for (vx_stamp* st : s->stamps) { c->be.free(st->mem); delete st; }
-	c->be.free(s->count); c->be.free(s->slotOf); c->be.free(s->buf); c->be.free(s->slot);
-	delete s;
-	c->stampState = nullptr;
-}
-
-StampState* stamp_state(vx_ctx* c)
-{
-	if (!c->stampState) { c->stampState = new StampState(); c->stampFree = stamp_state_free; }
-	return (StampState*)c->stampState;
-}
 
 bool stamp_owned(const vx_ctx* c, const vx_stamp* st)
 {
-	const StampState* s = (const StampState*)c->stampState;
+	const StampState* s = module_peek<StampState>(c, MOD_STAMP);
 	return s && st && std::find(s->stamps.begin(), s->stamps.end(), st) != s->stamps.end();
 }
 
@@ -288,7 +278,7 @@ int vx_stamp_capture(vx_ctx* c, const vx_box* box, vx_stamp** out)
 	RecBox b;
 	memcpy(&b, box, sizeof(b));
 	const u32 size[3] = { b.hi[0] - b.lo[0], b.hi[1] - b.lo[1], b.hi[2] - b.lo[2] };
-	StampState* s = stamp_state(c);
+	StampState* s = module_state<StampState>(c, MOD_STAMP);
 	vx_stamp* st = stamp_new(c, size);
 	if (!st) return fail(c, VX_ERR_DEVICE, what + "allocation failed: " + c->be.error());
 	const u32 wide = (b.lo[0] % 16u == 0u && size[0] % 16u == 0u) ? 1u : 0u;
@@ -310,7 +300,7 @@ int vx_stamp_upload(vx_ctx* c, const uint32_t size[3], const int8_t* dist, const
 	if (!out) return fail(c, VX_ERR_INVALID, what + "null out pointer");
 	if (const char* bad = stamp_check_size(size)) return fail(c, VX_ERR_INVALID, what + bad);
 	if (!dist) return fail(c, VX_ERR_INVALID, what + "null distance array");
-	StampState* s = stamp_state(c);
+	StampState* s = module_state<StampState>(c, MOD_STAMP);
 	vx_stamp* st = stamp_new(c, size);
 	if (!st) return fail(c, VX_ERR_DEVICE, what + "allocation failed: " + c->be.error());
 	u8* base = (u8*)st->mem;
@@ -355,8 +345,8 @@ int vx_stamp_info_get(vx_ctx* c, const vx_stamp* st, vx_stamp_info* info)
 void vx_stamp_free(vx_ctx* c, vx_stamp* st)
 {
 	VX_ENTER(c);
-	if (!c || !st || !c->stampState) return;
-	StampState* s = (StampState*)c->stampState;
+	if (!c || !st || !module_peek<StampState>(c, MOD_STAMP)) return;
+	StampState* s = module_peek<StampState>(c, MOD_STAMP);
 	auto it = std::find(s->stamps.begin(), s->stamps.end(), st);
 	if (it == s->stamps.end()) return;
 	s->stamps.erase(it);
@@ -380,7 +370,7 @@ int vx_paste_box(const vx_paste* paste, const uint32_t stamp_size[3], uint32_t n
 int vx_debug_paste_list_cap(vx_ctx* c, uint32_t cap)
 {
 	if (!c) return VX_ERR_INVALID;
-	stamp_state(c)->listCap = cap ? cap : (size_t)BRUSH_LIST_CAP;
+	module_state<StampState>(c, MOD_STAMP)->listCap = cap ? cap : (size_t)BRUSH_LIST_CAP;
 	return VX_OK;
 }
 
@@ -404,7 +394,7 @@ int vx_grid_paste(vx_ctx* c, vx_stamp* const* stamps, uint32_t n_stamps, const v
 	if (const char* bad = paste_check((const Paste*)pastes, count, size3, n_stamps)) return fail(c, VX_ERR_INVALID, what + bad);
 	if (!count) return VX_OK;
 
-	StampState* s = stamp_state(c);
+	StampState* s = module_state<StampState>(c, MOD_STAMP);
 	const u32 nb = c->n / 16;
 	const size_t blocks = (size_t)nb * nb * nb;
 	PastePlan& plan = s->plan;

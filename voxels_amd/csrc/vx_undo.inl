@@ -35,24 +35,14 @@ struct UndoState {
 	size_t listCap = 0;
 	void* slot = nullptr;      // RecSwapSlot
 	std::vector<void*> retired; // allocations a trim replaced while its copy out of them was still queued (undo_release)
+
+	void release(vx_ctx* c)
+	{
+		for (vx_record* r : records) { c->be.free(r->mem); delete r; }
+		for (void* p : retired) c->be.free(p);
+		c->be.free(bits); c->be.free(list); c->be.free(slot);
+	}
 };
-
-void undo_free(vx_ctx* c)
-{
-	UndoState* s = (UndoState*)c->undoState;
-	if (!s) return;
-	for (vx_record* r : s->records) { c->be.free(r->mem); delete r; }
-	for (void* p : s->retired) c->be.free(p);
-	c->be.free(s->bits); c->be.free(s->list); c->be.free(s->slot);
-	delete s;
-	c->undoState = nullptr;
-}
-
-UndoState* undo_state(vx_ctx* c)
-{
-	if (!c->undoState) { c->undoState = new UndoState(); c->undoFree = undo_free; }
-	return (UndoState*)c->undoState;
-}
 
 // behind a wait for the stream: what a trim retired is no longer read
 void undo_release(vx_ctx* c, UndoState* s)
@@ -61,16 +51,7 @@ void undo_release(vx_ctx* c, UndoState* s)
 	s->retired.clear();
 }
 
-bool undo_grow(vx_ctx* c, void*& p, size_t& cap, size_t need)
-{
-	if (need <= cap) return true;
-	c->be.free(p);
-	cap = need + need / 4;
-	p = c->be.alloc(cap);
-	if (!p) { cap = 0; return false; }
-	return true;
-}
-
+// (these two are also used by vx_stamp.inl and vx_measure.inl)
 bool undo_whole_grid(const vx_ctx* c) { return c->ownsGrid && c->n && c->zBegin == 0 && c->zEnd == c->n && c->yBegin == 0 && c->yEnd == c->n; }
 
 RecGrid undo_grid(const vx_ctx* c)
@@ -231,7 +212,7 @@ u32 rec_groups(u32 blocks) { return (blocks + REC_GROUP - 1u) / REC_GROUP; }
 bool undo_bitmap(vx_ctx* c, UndoState* s, size_t bitCount, u32*& bits, u32*& prefix, u32& words)
 {
 	words = (u32)((bitCount + 31u) / 32u);
-	if (!undo_grow(c, s->bits, s->bitsCap, ((size_t)words * 2u + 1u) * 4u)) return false;
+	if (!dev_grow(c, s->bits, s->bitsCap, ((size_t)words * 2u + 1u) * 4u)) return false;
 	bits = (u32*)s->bits; prefix = bits + words;
 	return c->be.fill(bits, 0, (size_t)words * 4u);
 }
@@ -254,7 +235,7 @@ int vx_grid_capture(vx_ctx* c, const vx_box* boxes, uint32_t count, vx_record** 
 	if (!undo_whole_grid(c)) return fail(c, VX_ERR_INVALID, what + "needs a whole grid owned by the context (vx_grid_upload / vx_grid_upload_packed)");
 	if (const char* bad = rec_check_boxes(c->n, (const RecBox*)boxes, count)) return fail(c, VX_ERR_INVALID, what + bad);
 
-	UndoState* s = undo_state(c);
+	UndoState* s = module_state<UndoState>(c, MOD_UNDO);
 	vx_record* r = new vx_record();
 	r->owner = c; r->n = c->n;
 	auto keep = [&]() { s->records.push_back(r); *out = r; return VX_OK; };
@@ -265,7 +246,7 @@ int vx_grid_capture(vx_ctx* c, const vx_box* boxes, uint32_t count, vx_record** 
 	auto noMemory = [&]() { delete r; return fail(c, VX_ERR_DEVICE, what + "allocation failed: " + c->be.error()); };
 	auto deviceFailed = [&]() { c->be.free(r->mem); delete r; return fail(c, VX_ERR_DEVICE, what + "device pass failed: " + c->be.error()); };
 	u32 *bits, *prefix, words;
-	if (!undo_grow(c, s->list, s->listCap, (size_t)count * sizeof(RecBox)) || !undo_bitmap(c, s, (size_t)nb * nb * nb, bits, prefix, words)) return noMemory();
+	if (!dev_grow(c, s->list, s->listCap, (size_t)count * sizeof(RecBox)) || !undo_bitmap(c, s, (size_t)nb * nb * nb, bits, prefix, words)) return noMemory();
 	if (!c->be.h2d(s->list, boxes, (size_t)count * sizeof(RecBox))) return deviceFailed();
 	u32 most = 0;
 	for (u32 i = 0; i < count; ++i) most = std::max(most, rec_box_runs(((const RecBox*)boxes)[i]));
@@ -297,12 +278,12 @@ int vx_record_trim(vx_ctx* c, vx_record* r, uint32_t* dropped)
 	if (const char* bad = undo_check(c, r)) return fail(c, VX_ERR_INVALID, what + bad);
 	if (!r->blocks) return VX_OK;
 
-	UndoState* s = undo_state(c);
+	UndoState* s = module_state<UndoState>(c, MOD_UNDO);
 	hipStream_t st = c->be.stream;
 	const u32 groups = rec_groups(r->blocks);
 	u32 *bits, *prefix, words;
 	// (one bit per entry, written a byte per group: the bitmap has a byte for every group)
-	if (!undo_bitmap(c, s, (size_t)groups * 8u, bits, prefix, words) || !undo_grow(c, s->list, s->listCap, (size_t)r->blocks * 4u))
+	if (!undo_bitmap(c, s, (size_t)groups * 8u, bits, prefix, words) || !dev_grow(c, s->list, s->listCap, (size_t)r->blocks * 4u))
 		return fail(c, VX_ERR_DEVICE, what + "allocation failed: " + c->be.error());
 	auto deviceFailed = [&]() { return fail(c, VX_ERR_DEVICE, what + "device pass failed: " + c->be.error()); };
 	const RecView old = rec_view(r->mem, r->blocks);
@@ -339,7 +320,7 @@ int vx_record_swap(vx_ctx* c, vx_record* r, vx_swap_result* result)
 	if (const char* bad = undo_check(c, r)) return fail(c, VX_ERR_INVALID, what + bad);
 	if (!r->blocks) { ++r->swaps; return VX_OK; }
 
-	UndoState* s = undo_state(c);
+	UndoState* s = module_state<UndoState>(c, MOD_UNDO);
 	if (!s->slot && !(s->slot = c->be.alloc(sizeof(RecSwapSlot)))) return fail(c, VX_ERR_DEVICE, what + "allocation failed: " + c->be.error());
 	const RecView v = rec_view(r->mem, r->blocks);
 	bool ok = c->be.fill(s->slot, 0, sizeof(RecSwapSlot));
@@ -423,8 +404,8 @@ int vx_record_read_block(vx_ctx* c, const vx_record* r, uint32_t index, int8_t* 
 void vx_record_free(vx_ctx* c, vx_record* r)
 {
 	VX_ENTER(c);
-	if (!c || !r || r->owner != c || !c->undoState) return;
-	UndoState* s = (UndoState*)c->undoState;
+	if (!c || !r || r->owner != c || !module_peek<UndoState>(c, MOD_UNDO)) return;
+	UndoState* s = module_peek<UndoState>(c, MOD_UNDO);
 	auto it = std::find(s->records.begin(), s->records.end(), r);
 	if (it == s->records.end()) return;
 	s->records.erase(it);

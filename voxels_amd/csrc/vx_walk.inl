@@ -33,18 +33,14 @@ struct WalkState {
 	void* goals = nullptr;
 	size_t goalsCap = 0;
 	void* small = nullptr;    // WalkCounts, then the counters of one batch of sweeps
+
+	void release(vx_ctx* c)
+	{
+		c->be.free(volume); c->be.free(perTile); c->be.free(goals); c->be.free(small);
+	}
 };
 
 enum { WALK_SMALL_BYTES = 128, WALK_AT_COUNTERS = 64 };
-
-void walk_free(vx_ctx* c)
-{
-	WalkState* s = (WalkState*)c->walkState;
-	if (!s) return;
-	c->be.free(s->volume); c->be.free(s->perTile); c->be.free(s->goals); c->be.free(s->small);
-	delete s;
-	c->walkState = nullptr;
-}
 
 __global__ __launch_bounds__(WG) void k_walk_stand(GridView g, IslRegion r, WalkParams P, u16* stand, u32* tileStand, u32* F, WalkCounts* counts)
 {
@@ -138,17 +134,16 @@ int vx_grid_walk_field(vx_ctx* c, const vx_walk_query* query, const vx_walk_goal
 	WalkParams P;
 	if (const char* bad = walk_check(c->n, whole, (const WalkQuery*)query, goals, goal_count, counts, d_field, lo, hi, &P)) return fail(c, VX_ERR_INVALID, what + bad);
 
-	WalkState* s = (WalkState*)c->walkState;
-	if (!s) { s = new WalkState(); c->walkState = s; c->walkFree = walk_free; }
+	WalkState* s = module_state<WalkState>(c, MOD_WALK);
 	const IslRegion r = isl_region(c->n, lo, hi);
 	const u32 tiles = isl_tiles(r);
 	const size_t V = (size_t)r.ext[0] * r.ext[1] * r.ext[2];
 	auto noMemory = [&]() { return fail(c, VX_ERR_DEVICE, what + "allocation failed: " + c->be.error()); };
 	if (!s->small && !(s->small = c->be.alloc(WALK_SMALL_BYTES))) return noMemory();
-	if (!d_field && !island_grow(c, s->volume, s->volumeCap, V * 4)) return noMemory();
+	if (!d_field && !dev_grow(c, s->volume, s->volumeCap, V * 4)) return noMemory();
 	const size_t atStand = 0, atCount = (size_t)tiles * 512, atFlags = atCount + (size_t)tiles * 4;
-	if (!island_grow(c, s->perTile, s->perTileCap, atFlags + (size_t)tiles * 8)) return noMemory();
-	if (goal_count && !island_grow(c, s->goals, s->goalsCap, (size_t)goal_count * sizeof(WalkGoal))) return noMemory();
+	if (!dev_grow(c, s->perTile, s->perTileCap, atFlags + (size_t)tiles * 8)) return noMemory();
+	if (goal_count && !dev_grow(c, s->goals, s->goalsCap, (size_t)goal_count * sizeof(WalkGoal))) return noMemory();
 
 	u32* F = d_field ? d_field : (u32*)s->volume;
 	u16* stand = (u16*)((char*)s->perTile + atStand);
