@@ -652,6 +652,84 @@ int  vx_record_measure(vx_ctx* ctx, const vx_record* record, vx_record_delta* de
 int  vx_debug_measure_chunk(vx_ctx* ctx, uint32_t pairs);
 int  vx_debug_measure_shortcuts(vx_ctx* ctx, uint32_t enable);
 
+/* ---- height maps (HIP library only) -------------------------------------------------------------------------------------
+ * How high is the ground at (x, y), and what is it made of: the surface heights per column of a voxel box of the resident grid,
+ * from the top or from the bottom, up to VX_HEIGHT_MAX_LAYERS surfaces per column, with the material byte of each - what
+ * vx_grid_create_heightmap takes, given back after brushes, pastes, smoothing and island removal.  Everything is integer and
+ * exact; no result depends on an order or a schedule.  voxels_amd/csrc/tv_height.h is the per-row and per-column logic;
+ * tests/height_oracle.py states this text again in numpy.  Needs a context that owns a whole grid (vx_grid_upload /
+ * vx_grid_upload_packed / vx_grid_create_*), as the brushes.
+ *   Solid      a voxel whose distance sample is < 0; zero is air (the definition of vx_grid_islands and vx_grid_measure).  The
+ *              dense fields are what is read; the mirrors and the BF_Empty flags play no part in the result.
+ *   Query      box = [lo, hi) in grid coordinates, internal axes (Z up), lo < hi <= n per axis, not necessarily aligned to
+ *              blocks; direction = VX_HEIGHT_FROM_TOP or VX_HEIGHT_FROM_BOTTOM; layers = 1..VX_HEIGHT_MAX_LAYERS; flags = 0 or
+ *              VX_HEIGHT_COUNT_SURFACES; the reserved words are zero.
+ *   Column     the samples (x, y, z0 .. z1 - 1) of the box for one (x, y), z0 = lo[2], z1 = hi[2].  Whatever lies outside
+ *              [z0, z1) counts as air, also where the grid goes on.
+ *   Surface    from the top: a z of the column that is solid, with z + 1 == z1 or sample z + 1 not solid; the surfaces of a
+ *              column are ordered by descending z.  From the bottom: a z that is solid, with z == z0 or sample z - 1 not solid;
+ *              ordered by ascending z.  Layer j is the j-th of them.
+ *   Height     a uint32_t in 24.8 fixed point.  With d0 (-128..-1) the surface sample and d1 (0..127) its air neighbour in the
+ *              scan direction, f = (256 * -d0) / (d1 - d0) in integer division, 2..256; from the top h = z * 256 + f, from the
+ *              bottom h = z * 256 - f.  A clipped surface is one whose air neighbour is the box's end: h = z * 256.
+ *              VX_HEIGHT_NONE stands where the column has fewer surfaces than the layer asks for.  A clipped height and a
+ *              crossing with d1 = 0 one sample further in can be the same number (from the top: clipped at z gives z * 256, and
+ *              so does a surface at z - 1 with d1 = 0); counts.clipped tells whether layer 0 holds any clipped surface.
+ *   Outputs    heights, layers * H * W entries with W = hi[0] - lo[0] and H = hi[1] - lo[1], layer-major, then y, then x.
+ *              materials (may be NULL), as many bytes: the material byte of the surface voxel, 0 where the height is
+ *              VX_HEIGHT_NONE.  surfaces (may be NULL; must be NULL unless VX_HEIGHT_COUNT_SURFACES is set), H * W entries: the
+ *              number of surfaces in the column.
+ *   Counts     (may be NULL) columns = W * H; covered = columns with at least one surface; surfaces = the sum over the
+ *              columns; min_height / max_height over layer 0 of the covered columns, zeros when there are none; clipped =
+ *              columns whose layer 0 is clipped; max_surfaces = the most surfaces in one column.  Without
+ *              VX_HEIGHT_COUNT_SURFACES surfaces and max_surfaces are 0, and the walk may stop as soon as every column of a
+ *              tile has its layers.
+ * vx_grid_heightmap takes host arrays, is synchronous, runs on the context's stream (vx_set_stream) and waits for the device
+ * once, at its end.  vx_grid_heightmap_device takes the three arrays as device pointers (heights 4-byte aligned, surfaces
+ * 2-byte) and counts on the host; with counts == NULL it only enqueues on the context's stream and does not wait - the
+ * per-frame form.
+ * Neither call changes the grid, the flags, the mirrors or any kept state: a full run afterwards replays what it replayed
+ * before.
+ * Everything is checked before anything is launched and nothing is written on an error: VX_ERR_INVALID for a null context,
+ * query or heights array, lo >= hi or hi > n on any axis, direction > 1, layers of 0 or above VX_HEIGHT_MAX_LAYERS, an unknown
+ * flag bit, a non-zero reserved word, a surfaces array without VX_HEIGHT_COUNT_SURFACES, a misaligned device array, a context
+ * that does not own a whole grid (slab and attached contexts, as for the brushes).  VX_ERR_DEVICE when working memory cannot be
+ * allocated.
+ * Working memory, kept with the context, grown when a call needs more and released with the context: 256 bytes for the counts,
+ * and for vx_grid_heightmap the staging of its results on the device - 4 bytes per entry of heights, 1 per entry of materials
+ * and 2 per column of surfaces where they are asked for, each part rounded up to 256 bytes.  vx_grid_heightmap_device with
+ * counts == NULL uses none. */
+#define VX_HEIGHT_MAX_LAYERS 8u
+#define VX_HEIGHT_NONE 0xFFFFFFFFu
+#define VX_HEIGHT_FROM_TOP 0u
+#define VX_HEIGHT_FROM_BOTTOM 1u
+#define VX_HEIGHT_COUNT_SURFACES 1u
+typedef struct vx_height_query {       /* 48 bytes */
+    vx_box   box;                      /* [lo, hi), grid coordinates, internal axes */
+    uint32_t direction;                /* VX_HEIGHT_FROM_TOP / VX_HEIGHT_FROM_BOTTOM */
+    uint32_t layers;                   /* 1..VX_HEIGHT_MAX_LAYERS */
+    uint32_t flags;                    /* VX_HEIGHT_COUNT_SURFACES */
+    uint32_t reserved[3];              /* 0 */
+} vx_height_query;
+typedef struct vx_height_counts {      /* 48 bytes */
+    uint64_t columns;                  /* W * H */
+    uint64_t covered;                  /* columns with at least one surface */
+    uint64_t surfaces;                 /* the sum over the columns; 0 without VX_HEIGHT_COUNT_SURFACES */
+    uint32_t min_height, max_height;   /* over layer 0 of the covered columns; zeros when there are none */
+    uint32_t clipped;                  /* columns whose layer 0 is clipped */
+    uint32_t max_surfaces;             /* 0 without VX_HEIGHT_COUNT_SURFACES */
+    uint32_t reserved[2];              /* 0 */
+} vx_height_counts;
+int  vx_grid_heightmap(vx_ctx* ctx, const vx_height_query* query, uint32_t* heights /* host, layers * H * W */,
+                       uint8_t* materials /* host, layers * H * W, may be NULL */, uint16_t* surfaces /* host, H * W, may be NULL */,
+                       vx_height_counts* counts /* host, may be NULL */);
+int  vx_grid_heightmap_device(vx_ctx* ctx, const vx_height_query* query, uint32_t* d_heights /* device */,
+                              uint8_t* d_materials /* device, may be NULL */, uint16_t* d_surfaces /* device, may be NULL */,
+                              vx_height_counts* counts /* host, may be NULL: enqueue only */);
+/* tests: whether the per-block sign summaries may stand in for distance rows (the default: yes); nothing of a result depends on
+ * it */
+int  vx_debug_height_shortcuts(vx_ctx* ctx, uint32_t enable);
+
 /* MaterialMap::GetMaterial resolved on the host (include/MaterialMap.h:19-30): lut[id] = {DiffuseIds0[3],
  * DiffuseIds1[3]}, valid[id] == 0 means GetMaterial returned NULL (texture bytes stay 0). */
 int vx_material_lut(vx_ctx* ctx, const uint8_t* lut /*256*6*/, const uint8_t* valid /*256*/);

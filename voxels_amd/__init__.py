@@ -13,7 +13,8 @@ from .binding import (BLOCK_INFO_DTYPE, BOX_DTYPE, DRAW_INDEXED_DTYPE, HIT_DTYPE
                       brush_boxes, hip_library_path, lod_params, lod_ranges, overlap_boxes, scatter_params, walk_query,
                       PASTE_COUNTS_DTYPE, PASTE_DTYPE, PASTE_MAX_COUNT, PASTE_MAX_STAMPS, PASTE_PAINT, PASTE_REPLACE, PASTE_RESULT_DTYPE, PASTE_SUBTRACT, PASTE_UNION,
                       STAMP_INFO_DTYPE, STAMP_MAX_EDGE, STAMP_MAX_VOXELS, Stamp, paste_boxes, pastes,
-                      MEASURE_DTYPE, MEASURE_MAX_BOXES, RECORD_DELTA_DTYPE)
+                      MEASURE_DTYPE, MEASURE_MAX_BOXES, RECORD_DELTA_DTYPE,
+                      HEIGHT_COUNTS_DTYPE, HEIGHT_COUNT_SURFACES, HEIGHT_FROM_BOTTOM, HEIGHT_FROM_TOP, HEIGHT_MAX_LAYERS, HEIGHT_NONE, HEIGHT_QUERY_DTYPE, height_query)
 
 __all__ = ["BLOCK_INFO_DTYPE", "BOX_DTYPE", "DRAW_INDEXED_DTYPE", "HIT_DTYPE", "LOD_COUNTS_DTYPE", "LOD_DRAW_DTYPE", "POINT_HIT_DTYPE", "POINT_QUERY_DTYPE",
            "RAY_DTYPE", "SCATTER_COUNTS_DTYPE", "SCATTER_PARAMS_DTYPE", "SCATTER_POINT_DTYPE", "SCATTER_RANGE_DTYPE", "SPHERE_CAST_DTYPE", "SPHERE_HIT_DTYPE", "VERTEX_DTYPE",
@@ -23,4 +24,5 @@ __all__ = ["BLOCK_INFO_DTYPE", "BOX_DTYPE", "DRAW_INDEXED_DTYPE", "HIT_DTYPE", "
            "OVERLAP_BOX_DTYPE", "OVERLAP_TRI_DTYPE", "OVERLAP_RANGE_DTYPE", "OVERLAP_COUNTS_DTYPE", "OVERLAP_MAX_QUERIES", "overlap_boxes",
            "STAMP_INFO_DTYPE", "PASTE_DTYPE", "PASTE_RESULT_DTYPE", "PASTE_COUNTS_DTYPE", "STAMP_MAX_EDGE", "STAMP_MAX_VOXELS", "PASTE_MAX_COUNT", "PASTE_MAX_STAMPS",
            "PASTE_REPLACE", "PASTE_UNION", "PASTE_SUBTRACT", "PASTE_PAINT", "Stamp", "paste_boxes", "pastes",
-           "MEASURE_DTYPE", "RECORD_DELTA_DTYPE", "MEASURE_MAX_BOXES"]
+           "MEASURE_DTYPE", "RECORD_DELTA_DTYPE", "MEASURE_MAX_BOXES",
+           "HEIGHT_QUERY_DTYPE", "HEIGHT_COUNTS_DTYPE", "HEIGHT_MAX_LAYERS", "HEIGHT_NONE", "HEIGHT_FROM_TOP", "HEIGHT_FROM_BOTTOM", "HEIGHT_COUNT_SURFACES", "height_query"]

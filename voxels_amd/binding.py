@@ -84,6 +84,13 @@ RECORD_DELTA_DTYPE = np.dtype([("removed_voxels", "<u8"), ("added_voxels", "<u8"
                                ("blocks", "<u4"), ("reserved", "<u4", 3)])
 assert MEASURE_DTYPE.itemsize == 48 and RECORD_DELTA_DTYPE.itemsize == 64
 MEASURE_MAX_BOXES = 1 << 16
+# height maps (include/voxels_hip.h, "height maps")
+HEIGHT_QUERY_DTYPE = np.dtype([("box", BOX_DTYPE), ("direction", "<u4"), ("layers", "<u4"), ("flags", "<u4"), ("reserved", "<u4", 3)])
+HEIGHT_COUNTS_DTYPE = np.dtype([("columns", "<u8"), ("covered", "<u8"), ("surfaces", "<u8"), ("min_height", "<u4"), ("max_height", "<u4"),
+                                ("clipped", "<u4"), ("max_surfaces", "<u4"), ("reserved", "<u4", 2)])
+assert HEIGHT_QUERY_DTYPE.itemsize == 48 and HEIGHT_COUNTS_DTYPE.itemsize == 48
+HEIGHT_MAX_LAYERS, HEIGHT_NONE = 8, 0xFFFFFFFF
+HEIGHT_FROM_TOP, HEIGHT_FROM_BOTTOM, HEIGHT_COUNT_SURFACES = 0, 1, 1
 SPHERE_STARTED_IN_CONTACT = 1
 # vx_lod_params / vx_lod_draw / vx_draw_indexed / vx_lod_counts (include/voxels_hip.h, LOD selection)
 LOD_PARAMS_DTYPE = np.dtype([("camera", "<f4", 3), ("n_planes", "<u4"), ("planes", "<f4", (6, 4)), ("ranges", "<f4", 16)])
@@ -379,6 +386,15 @@ class HipLibrary:
             lib.vx_debug_measure_shortcuts.argtypes = [vp, u32]
             for name in measure_calls:
                 getattr(lib, name).restype = C.c_int
+        # height maps: HIP builds only, likewise
+        height_calls = ("vx_grid_heightmap", "vx_grid_heightmap_device", "vx_debug_height_shortcuts")
+        self.has_height = all(hasattr(lib, name) for name in height_calls)
+        if self.has_height:
+            lib.vx_grid_heightmap.argtypes = [vp, vp, vp, vp, vp, vp]
+            lib.vx_grid_heightmap_device.argtypes = [vp, vp, vp, vp, vp, vp]
+            lib.vx_debug_height_shortcuts.argtypes = [vp, u32]
+            for name in height_calls:
+                getattr(lib, name).restype = C.c_int
         self.has_lod = hasattr(lib, "vx_lod_select")
         if self.has_lod:
             lib.vx_lod_select_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
@@ -409,6 +425,17 @@ def island_query(box=None, detached_only=False, remove=False, anchor_faces=0x3F,
     q["anchor_faces"] = anchor_faces
     q["max_voxels"] = max_voxels
     q["air_value"] = air_value
+    return q
+
+
+def height_query(box, direction="top", layers=1, count_surfaces=False):
+    """one HEIGHT_QUERY_DTYPE record; box = (lo, hi) in grid coordinates (internal axes, Z up); direction "top" / "bottom" (or
+    HEIGHT_FROM_TOP / HEIGHT_FROM_BOTTOM)"""
+    q = np.zeros(1, HEIGHT_QUERY_DTYPE)
+    q["box"]["lo"], q["box"]["hi"] = np.asarray(box[0], np.uint32), np.asarray(box[1], np.uint32)
+    q["direction"] = {"top": HEIGHT_FROM_TOP, "bottom": HEIGHT_FROM_BOTTOM}.get(direction, direction)
+    q["layers"] = layers
+    q["flags"] = HEIGHT_COUNT_SURFACES if count_surfaces else 0
     return q
 
 
@@ -775,6 +802,43 @@ class Polygonizer:
         self._check(self._lib.vx_grid_measure(self._h, _ptr(b) if b.size else None, b.size, _ptr(results) if b.size else None,
                                               _ptr(per_material) if tallies and b.size else None), "vx_grid_measure")
         return results, per_material
+
+    def heightmap(self, box, direction="top", layers=1, materials=True, count_surfaces=False):
+        """vx_grid_heightmap: the surfaces of the columns of box = (lo, hi) in grid coordinates (internal axes, Z up) ->
+        (heights uint32 [layers, H, W] in 24.8 fixed point, HEIGHT_NONE where a column has fewer surfaces; materials uint8
+        [layers, H, W] or None; surfaces uint16 [H, W] with count_surfaces, else None; the HEIGHT_COUNTS_DTYPE record)"""
+        if not self._L.has_height:
+            raise VoxelsHipError("this library has no height maps (HIP builds only)")
+        q = height_query(box, direction, layers, count_surfaces)
+        w, h = (int(q["box"]["hi"][0][k]) - int(q["box"]["lo"][0][k]) for k in (0, 1))
+        shape = (int(layers), max(h, 0), max(w, 0))
+        heights = np.zeros(shape, np.uint32)
+        mats = np.zeros(shape, np.uint8) if materials else None
+        surfaces = np.zeros(shape[1:], np.uint16) if count_surfaces else None
+        counts = np.zeros(1, HEIGHT_COUNTS_DTYPE)
+        self._check(self._lib.vx_grid_heightmap(self._h, _ptr(q), _ptr(heights), _ptr(mats), _ptr(surfaces), _ptr(counts)), "vx_grid_heightmap")
+        return heights, mats, surfaces, counts[0]
+
+    def heightmap_device(self, box, heights, direction="top", layers=1, materials=None, surfaces=None, counts=True):
+        """vx_grid_heightmap_device: as heightmap(), into device memory - heights (layers * H * W uint32), materials (as many
+        uint8, or None) and surfaces (H * W uint16, or None: given, it sets VX_HEIGHT_COUNT_SURFACES) are torch device tensors or
+        device addresses (ints).  counts=True: waits and returns the HEIGHT_COUNTS_DTYPE record; counts=False: only queued on the
+        context's stream (set_stream), returns None."""
+        if not self._L.has_height:
+            raise VoxelsHipError("this library has no height maps (HIP builds only)")
+        q = height_query(box, direction, layers, surfaces is not None)
+        cells = int(np.prod([max(int(q["box"]["hi"][0][k]) - int(q["box"]["lo"][0][k]), 0) for k in (0, 1)]))
+
+        def address(a, size, entries):
+            if a is None or isinstance(a, int):
+                return C.c_void_p(a)
+            assert a.is_cuda and a.is_contiguous() and a.element_size() == size and a.numel() == entries
+            return C.c_void_p(a.data_ptr())
+
+        rec = np.zeros(1, HEIGHT_COUNTS_DTYPE) if counts else None
+        self._check(self._lib.vx_grid_heightmap_device(self._h, _ptr(q), address(heights, 4, cells * int(layers)), address(materials, 1, cells * int(layers)),
+                                                       address(surfaces, 2, cells), _ptr(rec)), "vx_grid_heightmap_device")
+        return rec[0] if counts else None
 
     def capture_stamp(self, box):
         """vx_stamp_capture: the voxels of box = (lo, hi) in grid coordinates (internal axes, Z up) -> a Stamp"""

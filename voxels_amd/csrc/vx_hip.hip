@@ -4371,3 +4371,4 @@ struct Backend {
 #include "vx_lod.inl"
 #include "vx_scatter.inl"
 #include "vx_overlap.inl"
+#include "vx_height.inl"

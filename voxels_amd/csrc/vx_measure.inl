@@ -34,14 +34,20 @@ struct MeasureState {
 // The sign summaries (MirrorState::blockSign, field 0: 1 = every sample of the block is >= 0, 2 = every sample is < 0) describe
 // the dense fields while the mirrors are current: every device edit brings them up to date over the blocks it touched
 // (rebrick_blocks), and whatever writes the dense fields another way marks the mirrors stale.  Stale or absent: no shortcut.
+const u16* grid_block_signs(const vx_ctx* c)
+{
+	if (c->bricksStale || !c->dBlockSign || c->brickN != c->n) return nullptr;
+	return (const u16*)c->dBlockSign;
+}
+
+// ... for the measurements (the height maps read them under the same conditions, vx_height.inl)
 const u16* measure_signs(const vx_ctx* c, const MeasureState* s)
 {
 #if defined(VX_MEASURE_NO_SKIP)
 	(void)c; (void)s;
 	return nullptr;
 #else
-	if (!s->shortcuts || c->bricksStale || !c->dBlockSign || c->brickN != c->n) return nullptr;
-	return (const u16*)c->dBlockSign;
+	return s->shortcuts ? grid_block_signs(c) : nullptr;
 #endif
 }
 
