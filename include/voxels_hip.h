@@ -53,8 +53,8 @@ typedef struct vx_exec_info {
 	uint32_t levels;            /* LOD levels produced (PolygonSurface::GetLevelsCount) */
 	uint32_t retries;           /* re-runs after growing the output pools */
 	float device_ms;            /* device time of the last run, always > 0.  A full run on the single-stream path (three launches,
-	                             * or two while the slot plan is kept - then the first kernel is k_main, vx_slot_plan_counts;
-	                             * stage timing off): the device's constant 100 MHz clock, from the moment the first workgroup of
+	                             * or two while the slot plan is kept - then the first kernel is k_main, vx_slot_plan_counts -
+	                             * or k_main alone, vx_layout_keep_counts; stage timing off): the device's constant 100 MHz clock, from the moment the first workgroup of
 	                             * the first kernel starts to the publication of the run's header by the last kernel - a few
 	                             * microseconds less than the interval between two HIP events around the same launches, which also
 	                             * holds the first kernel's dispatch and the rest of the last kernel after the publication.  Every
@@ -1170,6 +1170,19 @@ int vx_material_inplace_counts(vx_ctx* ctx, uint64_t out[2]);
  * device_ms starts with k_main.  VX_PLAN=0 (read at context creation) keeps no plan: every run hands out its slots.
  * Diagnostics: tables, meshes, statistics and vx_exec_info are the same either way.  HIP builds only. */
 int vx_slot_plan_counts(vx_ctx* ctx, uint64_t out[2]);
+
+/* Full-run attempts of this context that kept the slot plan (vx_slot_plan_counts out[1], since the context was created) by their
+ * launches: out[0] = two, k_main and k_tail, out[1] = one, k_main alone - a run in place (vx_material_inplace_counts out[1]) on
+ * slots whose last accepted run left its mesh layout behind: every block's record, the block lists with their totals and the
+ * pool cursors, which depend on the grid, the BF_Empty flags, the level count and the slot plan alone (not on the material
+ * table: vx_material_lut keeps the layout).  Such a run writes every mesh where its record says it was, rebuilds no list, and
+ * its last workgroup publishes the header.  Whatever drops the slot plan drops the layout, and so do vx_compact_pools, pools
+ * that had to grow, and a run that handed a block to the general passes or met the large capacity class.
+ * VX_LAYOUT=0 (read at context creation) keeps no layout: every kept run is two launches.
+ * Diagnostics: block tables, mesh contents, statistics and vx_exec_info are the same either way.  The meshes' places in the pools
+ * (vx_level_ranges) are not: a run of two launches reserves them anew, in the order its blocks arrive, while a run of one launch
+ * writes every mesh where the run before left it - so with the layout kept the offsets stay the same from run to run.  HIP builds only. */
+int vx_layout_keep_counts(vx_ctx* ctx, uint64_t out[2]);
 
 /* The device forms of the exactness-critical arithmetic checked exhaustively on the GPU they run on (the reference does
  * this arithmetic on the host: t = (v1 << 8) / (v1 - v0), src/TransVoxelImpl.cpp:1591; normalizeFixZero, :93-103):

@@ -306,6 +306,10 @@ class HipLibrary:
         self.has_material_inplace = hasattr(lib, "vx_material_inplace_counts")
         if self.has_material_inplace:
             lib.vx_material_inplace_counts.argtypes = [vp, vp]
+        # (the mesh layout kept by runs in place - one launch: HIP builds only, and absent from builds made before it)
+        self.has_layout_keep = hasattr(lib, "vx_layout_keep_counts")
+        if self.has_layout_keep:
+            lib.vx_layout_keep_counts.argtypes = [vp, vp]
         lib.vx_selftest.argtypes = [vp, vp]
         lib.vx_stage_layout.argtypes = [vp, C.POINTER(C.c_int)]
         lib.vx_set_stage_timing.argtypes = [vp, C.c_int]
@@ -1391,4 +1395,13 @@ class Polygonizer:
             raise VoxelsHipError("this library has no vx_material_inplace_counts")
         out = np.zeros(2, np.uint64)
         self._check(self._lib.vx_material_inplace_counts(self._h, _ptr(out)), "vx_material_inplace_counts")
+        return int(out[0]), int(out[1])
+
+    def layout_keep_counts(self):
+        """vx_layout_keep_counts: (two launches, one launch) - the full-run attempts of this context that kept the slot plan, by
+        whether they also kept the mesh layout, cumulative.  HIP builds only: the CPU emulation library has no such entry point."""
+        if not self._L.has_layout_keep:
+            raise VoxelsHipError("this library has no vx_layout_keep_counts")
+        out = np.zeros(2, np.uint64)
+        self._check(self._lib.vx_layout_keep_counts(self._h, _ptr(out)), "vx_layout_keep_counts")
         return int(out[0]), int(out[1])

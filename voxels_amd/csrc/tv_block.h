@@ -142,6 +142,13 @@ enum { STAT_TR_PATHS = 20 };
 // [STAT_MAT_PATHS], [+ 1] = material blocks of a full run that were voted / that were replayed from the material store
 // (vx_material_path_counts); [STAT_MAT_MISS] = a replayed block found no entry in the store (the host repeats the run as a voting one)
 enum { STAT_MAT_PATHS = 22, STAT_MAT_MISS = 24 };
+// [STAT_LAYOUT_MISS] = a run that kept the mesh layout (MainPlan::layout, vx_main.inl) met a block whose totals are not its
+// record's, or handed a block to the general passes nobody runs behind it (the host drops the layout and repeats the run)
+enum { STAT_LAYOUT_MISS = 25 };
+// what a block of such a run takes for its pool offsets when its totals are not its record's: beyond any pool, so that the
+// capacity test in front of every mesh store keeps the block from writing (the host keeps no layout of pools that reach this
+// far; a block's totals stay below 2^18, so the sums do not wrap)
+enum : u32 { LAYOUT_MISS_OFF = 0xF0000000u };
 
 // The material store of one level >= 1 (GPU backend, vx_host.inl ensure_mat_store): what the material blocks of the last full
 // run on this grid left - cache, bitmap, cell count - by that run's own slot numbers, and the map from block coordinate to

@@ -124,7 +124,8 @@ __device__ __forceinline__ void f0_request(const GridView& g, const LevelDesc& L
 // SELF: nobody classified the block; the sign masks of its 19 x 19 sample rows (bit i = sample x = i, 0..16) are left in LDS
 // (on top of the vertex descriptors, which are written two barriers later) for f0_self_bits.
 // MAP: the bitmap came from the cell map; it is also stored to the block's slot (bitmap and consistency bits), where the
-// passes behind this one - the general pass, incremental runs, the accessors - look for it.
+// passes behind this one - the general pass, incremental runs, the accessors - look for it - unless the run keeps the mesh
+// layout (main_layout_kept): the slot still holds both, nothing is stored.
 template <bool SELF = false, bool MAP = false, typename ST>
 __device__ __forceinline__ u32 f0_deposit(ST& st, const LevelDesc& L, const R0Block& b, const F0Prefetch& pf)
 {
@@ -134,7 +135,7 @@ __device__ __forceinline__ u32 f0_deposit(ST& st, const LevelDesc& L, const R0Bl
 	if (!SELF) {
 		if (tid < 128) {
 			st.ntBits[tid] = pf.bits;
-			if (MAP) { L.ntBits[(size_t)b.slot * 128 + tid] = pf.bits; L.consBits[(size_t)b.slot * 128 + tid] = pf.bits; }
+			if (MAP && !main_layout_kept()) { L.ntBits[(size_t)b.slot * 128 + tid] = pf.bits; L.consBits[(size_t)b.slot * 128 + tid] = pf.bits; }
 		}
 	}
 	else if (tid == 0) st.zero = 0; // (the block's count of non-trivial cells is summed up here)
@@ -214,6 +215,8 @@ __device__ __forceinline__ R0Candidate f0_peek(const ExecParamsDev& p, const Lev
 template <int CAP, bool REMAP, bool SELF = false, bool MAP = false>
 __device__ __forceinline__ bool f0_next(const ExecParamsDev& p, const LevelDesc& L, u32 total, u32 lo, u32 stride, u32 limit, u32& it, R0Candidate c, R0Block& b)
 {
+	const bool layout = MAP && main_layout_kept(); // (the slot holds its bitmaps and its empty record already)
+
 	for (;;) {
 		if (SELF && r0_uniform(c.valid) && r0_uniform(c.skip)) {
 			// a block the emptiness rule skips (its empty record follows in r0_accept): no cells, nothing for its parent's vote
@@ -222,7 +225,7 @@ __device__ __forceinline__ bool f0_next(const ExecParamsDev& p, const LevelDesc&
 			((u16*)(L.consBits + (size_t)slot * 128))[threadIdx.x] = 0;
 			if (threadIdx.x == 0) L.ntCount[slot] = 0;
 		}
-		if (MAP && r0_uniform(c.valid)) {
+		if (MAP && !layout && r0_uniform(c.valid)) {
 			// a block this walk leaves alone - skipped by the emptiness rule or without cells (zeros; its empty record follows in
 			// r0_accept), or beyond this capacity class (few: the host repeats the run) - still gets its slot's bitmaps here
 			const u32 slot = r0_uniform(c.slot), ntc = r0_uniform(c.ntc), skip = r0_uniform(c.skip), coord = r0_uniform(c.coord);
@@ -233,7 +236,7 @@ __device__ __forceinline__ bool f0_next(const ExecParamsDev& p, const LevelDesc&
 				L.consBits[(size_t)slot * 128 + threadIdx.x] = w;
 			}
 		}
-		if (r0_accept<CAP>(L, lo, c, b)) return true;
+		if (r0_accept<CAP>(L, lo, c, b, !layout)) return true;
 		it += stride;
 		if (it >= limit) return false;
 		c = f0_peek<REMAP>(p, L, total, limit, it);
@@ -244,6 +247,9 @@ __device__ __forceinline__ bool f0_next(const ExecParamsDev& p, const LevelDesc&
 // `cur` writes its output.  Leaves the LDS state free behind a barrier-less tail (callers meet before they reuse it).
 // The parameters are kernel argument 0, read through kernarg_params(): every caller is a __global__ whose first parameter is
 // the unmodified ExecParamsDev.
+// MAP, in a run that keeps the mesh layout of the run before (MainPlan::layout, read where it is needed: main_layout_kept): a
+// block takes its pool ranges from its slot's record instead of reserving them, checks its totals against the record's
+// counts (a difference: nothing is written, STAT_LAYOUT_MISS is set) and stores neither record nor list count nor bitmaps.
 template <int CAP, bool REMAP, bool SELF = false, bool MAP = false>
 __device__ __forceinline__ void f0_walk(const F0Tables& T, Fast0State<CAP>& st, u32* wgStats, u32* zeroFlag, u32& parity,
                                         u32 total, u32 lo, u32 first, u32 stride, u32 limit, const int tid)
@@ -351,7 +357,8 @@ __device__ __forceinline__ void f0_walk(const F0Tables& T, Fast0State<CAP>& st, 
 				// last lane makes them: its wave owns the tail of the compact list and is the first to run out of cells.
 				if (tid == WG - 1) {
 					st.vTotal = vTotal; st.tTotal = tTotal;
-					reserve_both(p.P.cursors, vTotal, tTotal * 3u, st.vOff, st.iOff);
+					if (MAP && main_layout_kept()) layout_ranges(p, L.records[cur.slot], vTotal, tTotal * 3u, st.vOff, st.iOff);
+					else reserve_both(p.P.cursors, vTotal, tTotal * 3u, st.vOff, st.iOff);
 				}
 				for (u32 k0 = kBeg; k0 < kEnd; k0 += 64u) {
 					const u32 k = k0 + lane;
@@ -398,7 +405,8 @@ __device__ __forceinline__ void f0_walk(const F0Tables& T, Fast0State<CAP>& st, 
 					}
 				}
 			}
-			if (tid == 0) {
+			if (tid == 0 && MAP && main_layout_kept()) wgStats[0] += nt; // (the record and the list count are the run before's)
+			else if (tid == 0) {
 				BlockRecord& r = L.records[cur.slot];
 				r.coordId = cur.coord;
 				r.vOff = st.vOff; r.vCount = room ? st.vTotal : 0; r.iOff = st.iOff; r.iCount = room ? st.tTotal * 3u : 0;

@@ -51,6 +51,8 @@ typedef BrickSamplerT<u32> F1BrickSampler; // valid while a mirror is smaller th
 // launch; the lattice samples, which do not, are requested before the wait.  Otherwise (k_regular1_fast) `ntc` and `coord`
 // come from the run's flat list.  `gated` (uniform, run time; GATED only): false = a run in place (MainPlan::matMode 3) - the
 // slot holds what an earlier launch wrote, `ntc` is the caller's, nothing is waited for and the loads are ordinary ones.
+// GATED, in a run that keeps the mesh layout (MainPlan::layout, only with gated == false; main_layout_kept): pool ranges from the
+// slot's record, totals checked against it, no record and no list count stored (see f0_walk).
 template <int CAP, bool GATED>
 __device__ __forceinline__ void f1_block(const ExecParamsDev& p, const F0Tables& T, const F1BrickSampler& smp, Fast1State<CAP>& st, u32* wgStats, u32* zeroFlag, u32& parity,
                                          u32 level, u32 slot, u32 coord, u32 ntc, u32 lo, const int tid, const bool gated = GATED)
@@ -61,7 +63,7 @@ __device__ __forceinline__ void f1_block(const ExecParamsDev& p, const F0Tables&
 	if (!GATED || !gated) {
 		if (ntc > (u32)CAP || (lo && ntc <= lo)) return;    // another capacity class owns those (the first class, lo == 0, also owns the empty blocks)
 		if (ntc == 0) {                                     // (uniform) a surface-bearing block without a non-trivial coarse cell
-			if (tid == 0) reg_write_empty_record(L, slot);
+			if (tid == 0 && !(GATED && main_layout_kept())) reg_write_empty_record(L, slot);
 			return;
 		}
 	}
@@ -190,7 +192,8 @@ __device__ __forceinline__ void f1_block(const ExecParamsDev& p, const F0Tables&
 		if (tid == WG - 1) {
 			const u32 vTotal = tot & 0xFFFFu, tTotal = tot >> 16;
 			st.vTotal = vTotal; st.tTotal = tTotal;
-			reserve_both(p.P.cursors, vTotal, tTotal * 3u, st.vOff, st.iOff);
+			if (GATED && main_layout_kept()) layout_ranges(p, L.records[slot], vTotal, tTotal * 3u, st.vOff, st.iOff);
+			else reserve_both(p.P.cursors, vTotal, tTotal * 3u, st.vOff, st.iOff);
 		}
 		for (u32 k0 = kBeg; k0 < kEnd; k0 += 64u) {
 			const u32 k = k0 + lane;
@@ -245,15 +248,17 @@ __device__ __forceinline__ void f1_block(const ExecParamsDev& p, const F0Tables&
 			p.G.slowItems[1][atomicAdd(&p.G.slowCount[1], 1u)] = (level << 24) | slot;
 			atomicAdd(&p.G.slowCount[2], st.vTotal); atomicAdd(&p.G.slowCount[3], st.tTotal * 3u); // dead pool ranges (reported, vx_exec_info)
 		} else {
-			BlockRecord& r = L.records[slot];
-			r.coordId = coord;
-			r.vOff = st.vOff; r.vCount = room ? st.vTotal : 0; r.iOff = st.iOff; r.iCount = room ? st.tTotal * 3u : 0;
-			count_listed_block(L, r.coordId, r.vCount);
-			if (!L.hasTransitions) for (int f = 0; f < 6; ++f) { r.tvOff[f] = 0; r.tvCount[f] = 0; r.tiOff[f] = 0; r.tiCount[f] = 0; }
-			r.degenerate = 0;
-			r.ntCells = nt;
-			r.pad = 0;
-			if (!room) atomicOr(&p.P.cursors[CUR_OVF], 1u);
+			if (!(GATED && main_layout_kept())) { // (layout kept: the record and the list count are the run before's)
+				BlockRecord& r = L.records[slot];
+				r.coordId = coord;
+				r.vOff = st.vOff; r.vCount = room ? st.vTotal : 0; r.iOff = st.iOff; r.iCount = room ? st.tTotal * 3u : 0;
+				count_listed_block(L, r.coordId, r.vCount);
+				if (!L.hasTransitions) for (int f = 0; f < 6; ++f) { r.tvOff[f] = 0; r.tvCount[f] = 0; r.tiOff[f] = 0; r.tiCount[f] = 0; }
+				r.degenerate = 0;
+				r.ntCells = nt;
+				r.pad = 0;
+				if (!room) atomicOr(&p.P.cursors[CUR_OVF], 1u);
+			}
 			wgStats[0] += nt;
 			for (int i = 0; i < 16; ++i) wgStats[4 + i] += st.classCount[i];
 		}

@@ -18,6 +18,8 @@ template <bool WIDE, bool GATED>
 __device__ __forceinline__ bool trf_block(const ExecParamsDev& p, const RegBlockCtx& b, TrState& st, const Tables& T, u32* waveTot,
                                           const BrickSamplerT<typename std::conditional<WIDE, size_t, u32>::type>& smp, const int tid, bool& matReady, const bool preMat)
 {
+	// GATED, in a run that keeps the mesh layout (MainPlan::layout, main_layout_kept): the ranges come from the slot's record, the
+	// totals are checked against it, and no record is stored (see f0_walk)
 	const u32 lane = (u32)tid & 63u, wave = (u32)tid >> 6;
 	const LevelDesc& L = p.levels[b.level];
 
@@ -28,7 +30,7 @@ __device__ __forceinline__ bool trf_block(const ExecParamsDev& p, const RegBlock
 	const u32 nt = r0_uniform((u32)__shfl((int)incl, 63, 64));
 	if (r0_uniform(st.zero) != 0u || nt > (u32)TR_CAP) return false;
 	if (nt == 0u) {
-		if (tid == 0) tr_write_empty_record(L, b.slot);
+		if (tid == 0 && !(GATED && main_layout_kept())) tr_write_empty_record(L, b.slot);
 		return true;
 	}
 	{
@@ -105,7 +107,8 @@ __device__ __forceinline__ bool trf_block(const ExecParamsDev& p, const RegBlock
 		}
 		if (tid == WG - 1) {
 			st.vTotal = tot & 0xFFFFu; st.iTotal = tot >> 16;
-			reserve_both(p.P.cursors, tot & 0xFFFFu, tot >> 16, st.vOff, st.iOff);
+			if (GATED && main_layout_kept()) layout_ranges_faces(p, L.records[b.slot], 0, 6, tot & 0xFFFFu, tot >> 16, st.vOff, st.iOff);
+			else reserve_both(p.P.cursors, tot & 0xFFFFu, tot >> 16, st.vOff, st.iOff);
 		}
 		for (u32 k0 = kBeg; k0 < kEnd; k0 += 64u) {
 			const u32 k = k0 + lane;
@@ -145,7 +148,7 @@ __device__ __forceinline__ bool trf_block(const ExecParamsDev& p, const RegBlock
 			}
 		}
 	}
-	tr_phase_record(st, L, b, p.P, 0, 6, tid);
+	if (!(GATED && main_layout_kept())) tr_phase_record(st, L, b, p.P, 0, 6, tid); // (layout kept: the record is the run before's)
 	return true;
 }
 

@@ -1,7 +1,8 @@
 // vx_hip.hip — gfx950 (MI355X / CDNA4) kernels and HIP backend of libvoxels_hip.so.
 //
 // A full run of a terrain-like grid is THREE launches on one stream - and TWO, k_main | k_tail, while the grid
-// has not changed since a run handed out the slots (the slot plan, vx_host.inl: k_run_head's whole output is still in memory):
+// has not changed since a run handed out the slots (the slot plan, vx_host.inl: k_run_head's whole output is still in memory) -
+// and ONE, k_main alone, once such a run has also left its mesh layout behind (MainPlan::layout, vx_main.inl):
 //   k_run_head    what the BF_Empty flags and the sign summaries say about a block; the blocks that are not quiet get their
 //                 level-0 slots and their ancestors the slots of the levels above (workgroup = an aligned 8 x 8 x 4 box)
 //   k_main        (vx_main.inl) every block of every level: two queues handed out to persistent workgroups - the level-0
@@ -83,6 +84,12 @@ __device__ __forceinline__ const ExecParamsDev& kernarg_params()
 	return *(const ExecParamsDev*)kp;
 }
 
+// k_main only (its per-block bodies, under the template arguments no other kernel passes): MainPlan::layout of the running
+// launch - 1: the run keeps the mesh layout - read afresh from the kernarg segment wherever it decides something, like the
+// parameters above: a flag carried through a block's phases would be one more scalar register in bodies that have none to spare.
+// (Defined in vx_main.inl, behind MainPlan.)
+__device__ __forceinline__ bool main_layout_kept();
+
 constexpr int WG = 256;
 constexpr int REG_CAP_SMALL = LARGE_THRESHOLD; // LDS capacity class of the regular pass that covers ordinary surfaces
 constexpr int REG_CAP_MID = 1536;               // second class of the table-driven passes (dense surfaces: three workgroups per CU instead of one in the 4096-cell class)
@@ -154,6 +161,31 @@ __device__ __forceinline__ void reserve_both(u32* cursors, u32 verts, u32 indice
 {
 	const unsigned long long r = atomicAdd((unsigned long long*)cursors, (unsigned long long)verts | ((unsigned long long)indices << 32));
 	vOff = (u32)r; iOff = (u32)(r >> 32);
+}
+
+// A run that keeps the mesh layout (MainPlan::layout, vx_main.inl) reserves nothing: a block's ranges are where its slot's
+// record - written by the run before, on the same grid - says they are.  The totals the block has just computed must be the
+// record's counts; where they are not, the block gets ranges no pool holds (LAYOUT_MISS_OFF: it writes nothing) and the
+// run is marked (STAT_LAYOUT_MISS: the host drops the layout and repeats).  One lane, like the reservation.
+__device__ __forceinline__ void layout_take(u32* stats, u32 offV, u32 countV, u32 offI, u32 countI, u32 verts, u32 indices, u32& vOff, u32& iOff)
+{
+	const bool same = countV == verts && countI == indices;
+	if (!same) atomicOr(&stats[STAT_LAYOUT_MISS], 1u);
+	vOff = same ? offV : (u32)LAYOUT_MISS_OFF; iOff = same ? offI : (u32)LAYOUT_MISS_OFF;
+}
+__device__ __forceinline__ void layout_ranges(const ExecParamsDev& p, const BlockRecord& r, u32 verts, u32 indices, u32& vOff, u32& iOff)
+{
+	layout_take(p.G.stats, r.vOff, r.vCount, r.iOff, r.iCount, verts, indices, vOff, iOff);
+}
+// ... of the transition meshes of the faces [f0, f1), which one reservation covered (tr_phase_record: the first face's ranges
+// start where the reservation did - its first cell is cell 0 of the batch, base 0 - and the faces follow each other without a
+// gap, so the counts add up to the totals).  Only called for a batch with cells; a batch that overflowed or came out empty
+// left zeros, which no totals of a batch with cells equal unless they are zero as well.
+__device__ __forceinline__ void layout_ranges_faces(const ExecParamsDev& p, const BlockRecord& r, int f0, int f1, u32 verts, u32 indices, u32& vOff, u32& iOff)
+{
+	u32 cv = 0, ci = 0;
+	for (int f = f0; f < f1; ++f) { cv += r.tvCount[f]; ci += r.tiCount[f]; }
+	layout_take(p.G.stats, r.tvOff[f0], cv, r.tiOff[f0], ci, verts, indices, vOff, iOff);
 }
 
 // ---- dependencies between workgroups of ONE launch (k_main): LevelDesc::matDone ----------------------------------------
@@ -2424,6 +2456,9 @@ template <bool WIDE, bool GATED>
 __device__ __forceinline__ void tr_block(const ExecParamsDev& p, RegBlockCtx b, u32 coordId, TrState& st, const Tables& T, u32* scanScratch, u32* quietFaces, u32& quietParity,
                                          const BrickSamplerT<typename std::conditional<WIDE, size_t, u32>::type>& smp, int tid, const bool tables, u32* pathCount, const bool matKnown = true)
 {
+	// GATED, in a run that keeps the mesh layout (MainPlan::layout, vx_main.inl; main_layout_kept): either body takes its ranges from
+	// the slot's record and stores no record
+
 	// matKnown: the block's material cache is known to be complete - earlier launches wrote it (the stand-alone pass; inside
 	// k_main a run in place, MainPlan::matMode 3): nothing is waited for.  In the stand-alone pass its entries behind the
 	// transition cells are also requested with the planes (preMat).  Inside k_main they are fetched where they are used, with
@@ -2570,7 +2605,8 @@ __device__ __forceinline__ void tr_block(const ExecParamsDev& p, RegBlockCtx b, 
 				u32 resV = 0, resI = 0;
 				if (tid == 0) {
 					st.vTotal = vt; st.iTotal = it2;
-					reserve_both(p.P.cursors, vt, it2, resV, resI);
+					if (GATED && main_layout_kept()) layout_ranges_faces(p, L.records[b.slot], f0, f1, vt, it2, resV, resI);
+					else reserve_both(p.P.cursors, vt, it2, resV, resI);
 				}
 				tr_phase_describe(st, 0, tid, WG);
 				if (tid == 0) { st.vOff = resV; st.iOff = resI; }
@@ -2591,7 +2627,7 @@ __device__ __forceinline__ void tr_block(const ExecParamsDev& p, RegBlockCtx b, 
 				tr_phase_flush_indices(st, T, p.P, chunk, tid, WG);
 			}
 		}
-		tr_phase_record(st, L, b, p.P, f0, f1, tid);
+		if (!(GATED && main_layout_kept())) tr_phase_record(st, L, b, p.P, f0, f1, tid); // (layout kept: the record is the run before's)
 		f0 = f1;
 	}
 	__syncthreads();
@@ -2663,6 +2699,67 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WIDE ? 3 : T
 	if (threadIdx.x < 2 && pathCount[threadIdx.x]) atomicAdd(&p.G.stats[STAT_TR_PATHS + threadIdx.x], pathCount[threadIdx.x]); // (behind the last block's closing barrier)
 }
 
+// publish: the workgroup that finishes last copies the run's header (counters, totals, statistics; the block-class partial
+// sums behind it) into page-locked host memory - the host then needs no copy behind the run's last kernel (a blit kernel of
+// its own: ~3.5 us, and ~5.5 us until it starts), only the wait it does anyway.
+// The host may wait for the publication itself instead of the kernel's end (Backend::wait_published): the word `flagWord` of
+// the host copy is written last, by one lane, with the run's tag - after every other word left through write-through stores
+// that every storing wave waited for (the form of publish_done_through, at system scope: no fence, so no write-back of the
+// XCD's L2 - the list entries this launch just wrote sit there).  `clockWord` of the host copy receives the 100 MHz clock at the publication
+// (0: the header's own word), the end of device_ms; k_run_head stored its start into the header.
+struct HeaderPublish {
+	u32* done;         // counter of finished workgroups (a header word: zeroed with the run's counters)
+	u32* host;         // page-locked destination (nullptr: no publication)
+	const u32* dev;    // the header
+	u32 words;
+	u32 flagWord, flag; // the word of the host copy that says "published", and what it then holds (the run's tag, never 0)
+	u32 clockWord;
+};
+
+// every lane of the publishing workgroup
+__device__ __forceinline__ void publish_header_to_host(const HeaderPublish& pub, const u32 tid, const u32 lanes)
+{
+	const u32 now = run_clock();
+	for (u32 i = tid; i < pub.words; i += lanes) {
+		if (i == pub.flagWord) continue;
+		const u32 v = (pub.clockWord && i == pub.clockWord) ? now : TV_LOAD_THROUGH(pub.dev + i);
+		__hip_atomic_store(pub.host + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	}
+#if defined(VX_CONSERVATIVE_SYNC)
+	__threadfence_system();
+	__syncthreads();
+	if (tid == 0) __hip_atomic_store(pub.host + pub.flagWord, pub.flag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+#else
+	asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // every storing wave: its write-through stores have left
+	__syncthreads();
+	if (tid == 0) __hip_atomic_store(pub.host + pub.flagWord, pub.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+#endif
+}
+
+// The start state of a run that launches no k_run_head (the slot plan, vx_host.inl): every counter 0 - except the words the head
+// would have added into, which are taken from the current header, where they are final since this run's head (or were seeded
+// by the tail of the run before): the slot counts of the run's levels and the head's two statistics.
+struct SeedRanges {
+	u32* header;
+	u32 headerWords;
+	u32* listCounts;
+	u32 listWgs;
+	const u32* from;  // the current header
+	u32 levels;       // words [0, levels): the slot counts
+	u32 words[2];     // the head's statistics: "blocks read" (largeBlocks + 1), "blocks calculated" on level 0 (stats + 2)
+};
+
+// lane `first` of `lanes` (the list workgroups of k_tail; the last workgroup of a k_main that keeps the mesh layout)
+__device__ __forceinline__ void seed_words(const SeedRanges& seed, const u32 first, const u32 lanes)
+{
+	for (u32 i = first; i < seed.headerWords || i < seed.listWgs; i += lanes) {
+		if (i < seed.headerWords) {
+			const bool kept = i < seed.levels || i == seed.words[0] || i == seed.words[1];
+			seed.header[i] = kept ? TV_LOAD_THROUGH(seed.from + i) : 0u;
+		}
+		if (i < seed.listWgs) seed.listCounts[i] = 0;
+	}
+}
 
 } // namespace
 
@@ -2718,43 +2815,6 @@ __global__ __launch_bounds__(LIST_WG) void k_list_count(ExecParamsDev p, ListPla
 	const u32 id = (w - plan.wgStart[l]) * LIST_WG + threadIdx.x;
 	const int n = __syncthreads_count(listed_block_slot(p.levels[l], id) >= 0 ? 1 : 0);
 	if (threadIdx.x == 0) plan.counts[w] = (u32)n;
-}
-
-// publish: the workgroup that finishes last copies the run's header (counters, totals, statistics; the block-class partial
-// sums behind it) into page-locked host memory - the host then needs no copy behind the run's last kernel (a blit kernel of
-// its own: ~3.5 us, and ~5.5 us until it starts), only the wait it does anyway.
-// The host may wait for the publication itself instead of the kernel's end (Backend::wait_published): the word `flagWord` of
-// the host copy is written last, by one lane, with the run's tag - after every other word left through write-through stores
-// that every storing wave waited for (the form of publish_done_through, at system scope: no fence, so no write-back of the
-// XCD's L2 - the list entries this launch just wrote sit there).  `clockWord` of the host copy receives the 100 MHz clock at the publication
-// (0: the header's own word), the end of device_ms; k_run_head stored its start into the header.
-struct HeaderPublish {
-	u32* done;         // counter of finished workgroups (a header word: zeroed with the run's counters)
-	u32* host;         // page-locked destination (nullptr: no publication)
-	const u32* dev;    // the header
-	u32 words;
-	u32 flagWord, flag; // the word of the host copy that says "published", and what it then holds (the run's tag, never 0)
-	u32 clockWord;
-};
-
-// every lane of the publishing workgroup
-__device__ __forceinline__ void publish_header_to_host(const HeaderPublish& pub, const u32 tid, const u32 lanes)
-{
-	const u32 now = run_clock();
-	for (u32 i = tid; i < pub.words; i += lanes) {
-		if (i == pub.flagWord) continue;
-		const u32 v = (pub.clockWord && i == pub.clockWord) ? now : TV_LOAD_THROUGH(pub.dev + i);
-		__hip_atomic_store(pub.host + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-	}
-#if defined(VX_CONSERVATIVE_SYNC)
-	__threadfence_system();
-	__syncthreads();
-	if (tid == 0) __hip_atomic_store(pub.host + pub.flagWord, pub.flag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-#else
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // every storing wave: its write-through stores have left
-	__syncthreads();
-	if (tid == 0) __hip_atomic_store(pub.host + pub.flagWord, pub.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-#endif
 }
 
 // (workgroup w of listWgs: a launch of its own, or the workgroups of k_tail behind the general passes)
@@ -2835,19 +2895,6 @@ __global__ __launch_bounds__(LIST_WG) void k_list_write(ExecParamsDev p, ListPla
 // device-wide first (records and list counts are read by list workgroups on other XCDs: through write-through loads where
 // the list pass reads what this launch wrote).
 // ------------------------------------------------------------------------------------------------------
-// The start state of a run that launches no k_run_head (the slot plan, vx_host.inl): every counter 0 - except the words the head
-// would have added into, which are taken from the current header, where they are final since this run's head (or were seeded
-// by the tail of the run before): the slot counts of the run's levels and the head's two statistics.
-struct SeedRanges {
-	u32* header;
-	u32 headerWords;
-	u32* listCounts;
-	u32 listWgs;
-	const u32* from;  // the current header
-	u32 levels;       // words [0, levels): the slot counts
-	u32 words[2];     // the head's statistics: "blocks read" (largeBlocks + 1), "blocks calculated" on level 0 (stats + 2)
-};
-
 struct TailPlan {
 	u32 wgs0, wgs1, listWgs; // workgroups: general pass of level 0 | of the levels >= 1 | lists
 	u32 levels;
@@ -2906,16 +2953,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(3))) void k_
 			if (i < t.next.listWgs) t.next.listCounts[i] = 0;
 		}
 	}
-	if (t.seed.header) {
-		const u32 lanes = t.listWgs * WG;
-		for (u32 i = (role - general) * WG + threadIdx.x; i < t.seed.headerWords || i < t.seed.listWgs; i += lanes) {
-			if (i < t.seed.headerWords) {
-				const bool kept = i < t.seed.levels || i == t.seed.words[0] || i == t.seed.words[1];
-				t.seed.header[i] = kept ? TV_LOAD_THROUGH(t.seed.from + i) : 0u;
-			}
-			if (i < t.seed.listWgs) t.seed.listCounts[i] = 0;
-		}
-	}
+	if (t.seed.header) seed_words(t.seed, (role - general) * WG + threadIdx.x, t.listWgs * WG);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -3374,6 +3412,7 @@ struct Backend {
 		u32 matStore = 1;    // VX_MATSTORE=0: no material store - every full run votes the material caches of the levels >= 1
 		u32 plan = 1;        // VX_PLAN=0: no slot plan - every full run launches k_run_head
 		u32 matInPlace = 1;  // VX_MAT_INPLACE=0: a run that keeps the slot plan still copies the material caches from the store into their slots
+		u32 layout = 1;      // VX_LAYOUT=0: a run in place still reserves its pool ranges and is followed by k_tail (two launches, not one)
 		// fixed since round 6 (were environment variables while they were being measured; profiles/HISTORY.md has the sweeps)
 		static constexpr u32 classifyRowGroup = 4, regWgsPerCu = 20, f1WgsPerCu = 20, foldBlocks = 65536, upWgsPerCu = 5, mainWgsPerCu = 4, mainBatch = 2, mainUpperNum = 1, mainUpperDen = 4;
 		bool fast0() const { return (fast & 1u) != 0; }
@@ -3411,6 +3450,7 @@ struct Backend {
 		tune.matStore = env_u32("VX_MATSTORE", 1);
 		tune.plan = env_u32("VX_PLAN", 1);
 		tune.matInPlace = env_u32("VX_MAT_INPLACE", 1);
+		tune.layout = env_u32("VX_LAYOUT", 1);
 		hipDeviceProp_t prop;
 		if (hipGetDeviceProperties(&prop, device) == hipSuccess) cus = prop.multiProcessorCount;
 		if (!check(hipStreamCreateWithFlags(&ownStream, hipStreamNonBlocking), "hipStreamCreate")) { err = lastError; return false; }
@@ -3752,12 +3792,26 @@ struct Backend {
 	// ... and whether this run is such a run: its counters were seeded, its slots are in place - no k_reset, no k_run_head, and
 	// workgroup 0 of k_main leaves the clock (set per attempt by the host, cleared by the launch it applies to)
 	bool keepSlots = false;
+	// ... and whether it may also keep the mesh layout (MainPlan::layout; set per attempt by the host together with what the last
+	// workgroup of k_main then reports, cleared by run_main): then k_main is the run's only launch.  layoutRan: the launch was
+	// made that way (read by the host behind run_block_lists, which launches nothing then).
+	bool keepLayout = false, layoutRan = false;
+	LayoutEnd layoutEnd = {};
+	void set_layout_end(const u32 cursors[2], const u32* totals, u32* lists)
+	{
+		layoutEnd = LayoutEnd();
+		layoutEnd.cursors[0] = cursors[0]; layoutEnd.cursors[1] = cursors[1];
+		for (u32 l = 0; l < MAX_LEVELS; ++l) layoutEnd.totals[l] = totals[l];
+		layoutEnd.lists = lists;
+		keepLayout = true;
+	}
 	u32 headWorkgroups = 0; // of the last k_run_head launch: that many block-class partial sums sit behind the header
 	template <typename P>
 	void run_reset(const P& p, u32 levels, u32* header, u32 headerWords, u32* listCounts, u32 listWgs, bool alreadyClean = false)
 	{
 		ResetRanges r;
 		pendingClean = alreadyClean;
+		keepLayout = layoutRan = false; // (every attempt starts here: asked for behind this by set_layout_end, granted by run_main)
 		for (u32 l = 0; l < MAX_LEVELS; ++l) r.maps[l] = p.levels[l].slotOf;
 		u32 run = headerWords;
 		r.header = header; r.headerWords = headerWords;
@@ -4038,6 +4092,8 @@ struct Backend {
 		for (u32 l = 1; l < levels; ++l) items += (unsigned long long)p.levels[l].cap * ((mode == 3u ? 0u : 1u) + (l < plan.fastEnd ? 1u : 0u) + (p.levels[l].hasTransitions ? 1u : 0u));
 		if (withLevel0) items += p.levels[0].cap;
 		matModeUsed = 0;
+		const bool layoutAsked = keepLayout;
+		keepLayout = layoutRan = false;
 		if (!items) return;
 		// persistent workgroups; without the level-0 queue at most as many as the previous run had items (the host's hint; any
 		// number is correct - a workgroup that finds the queues empty leaves - but every workgroup costs a dequeue)
@@ -4046,15 +4102,26 @@ struct Backend {
 		if (emitFrom && withLevel0) {
 			// (no level-0 queue: the persistent workgroups are the upper queue's)
 			plan.level0 = 0u; plan.upperNum = plan.upperDen = 1u; plan.emitFrom = emitFrom;
-			launch_with_event(k_main<false, true>, dim3(grid), UP_TAB_LDS + MAIN_STATE_LDS, dev(p), plan, (u32*)nullptr);
+			launch_with_event(k_main<false, true>, dim3(grid), UP_TAB_LDS + MAIN_STATE_LDS, dev(p), plan, (u32*)nullptr, LayoutEnd());
 		} else if (withLevel0 && p.G.cellMap) {
 			plan.matMode = mode;
 			matModeUsed = plan.matMode;
+			// The mesh layout kept as well: a run in place whose header travels with this launch (the host has handed over the
+			// publication and the seed already) and whose every level has the table-driven regular body - nothing but k_tail
+			// would follow k_main, and nothing of k_tail's work is left but what LayoutEnd describes.
+			LayoutEnd end = LayoutEnd();
+			if (layoutAsked && mode == 3u && keepSlots && clockStart && publish.host && nextSeed.header && levels <= (u32)PYRAMID_LEVELS && !stageOn) {
+				plan.layout = 1u;
+				end = layoutEnd;
+				end.pub = publish;
+				end.seed = nextSeed;
+				layoutRan = true;
+			}
 			// (a run that keeps its slots has no head: the run's clock starts here)
-			launch_with_event(k_main<false, false, true>, dim3(grid), UP_TAB_LDS + MAIN_STATE_LDS, dev(p), plan, keepSlots ? clockStart : (u32*)nullptr);
+			launch_with_event(k_main<false, false, true>, dim3(grid), UP_TAB_LDS + MAIN_STATE_LDS, dev(p), plan, keepSlots ? clockStart : (u32*)nullptr, end);
 			keepSlots = false;
 		} else
-			launch_with_event(k_main<false>, dim3(grid), UP_TAB_LDS + (withLevel0 ? MAIN_STATE_LDS : UP_STATE_LDS), dev(p), plan, (u32*)nullptr);
+			launch_with_event(k_main<false>, dim3(grid), UP_TAB_LDS + (withLevel0 ? MAIN_STATE_LDS : UP_STATE_LDS), dev(p), plan, (u32*)nullptr, LayoutEnd());
 		check(hipGetLastError(), "k_main launch");
 	}
 
@@ -4104,7 +4171,7 @@ struct Backend {
 			items += v * (1u + (l < plan.fastEnd ? 1u : 0u) + (p.levels[l].hasTransitions ? 1u : 0u));
 			if (l >= plan.fastEnd) upperVol += v;
 		}
-		hipLaunchKernelGGL(k_main<true>, dim3(std::max<u32>(1u, std::min<u32>(items, slots))), dim3(WG), UP_TAB_LDS + MAIN_STATE_LDS, stream, dev(p), plan, (u32*)nullptr);
+		hipLaunchKernelGGL(k_main<true>, dim3(std::max<u32>(1u, std::min<u32>(items, slots))), dim3(WG), UP_TAB_LDS + MAIN_STATE_LDS, stream, dev(p), plan, (u32*)nullptr, LayoutEnd());
 		check(hipGetLastError(), "k_main (incremental) launch");
 		if (large0Expected || largeUpperExpected) {
 			// (level 0 and the levels above it are announced apart: the coarse levels of a terrain hold such blocks where level 0
@@ -4176,6 +4243,7 @@ struct Backend {
 			// capacity classes, what they hand on, levels beyond the lattice copies - follows on the same stream, and so do the
 			// block lists and the header read-back: no second stream, no event
 			run_main(p, levels, true);
+			if (layoutRan) { overlappedTail = false; return; } // (the run's one launch, MainPlan::layout)
 			upperDone = level0Done = true;
 			tailWgs[0] = tailWgs[1] = 0;
 			tailPending = tailDone && p.levels[0].listCounts;
@@ -4318,6 +4386,12 @@ struct Backend {
 		const bool tail = tailPending;
 		tailPending = false;
 		tailCleaned = tailSeeded = false;
+		if (layoutRan) {
+			// the lists are in place, and the last workgroup of k_main seeds and publishes (LayoutEnd): nothing is launched
+			tailSeeded = true;
+			nextReset.header = nextSeed.header = nullptr;
+			return pub.host != nullptr;
+		}
 		if (tail) {
 			// (with or without list workgroups: the general passes were left to this launch)
 			TailPlan t;

@@ -123,6 +123,16 @@ struct vx_ctx {
 	bool planOn = false, planValid = false;
 	u32 planLevels = 0;
 	uint64_t planRuns[2] = { 0, 0 };
+	// The mesh layout (backends with VX_BACKEND_SLOT_PLAN; MainPlan::layout): what a full run on the plan's slots leaves besides
+	// the meshes - every slot's record, the block lists and their totals, the final pool cursors - depends on the grid, the
+	// BF_Empty flags, the level count and the slot plan alone, but for the pool offsets, which blocks reserve in the order they
+	// arrive.  valid = an accepted run on the plan's slots has left all of that where it wrote it and nothing has touched it
+	// since (vx_polygonize, where it is decided, lists the writers): a run in place then takes every block's ranges from its
+	// record, launches k_main alone and reports layoutCursors and layoutTotals, taken from the header of the run that left the
+	// layout.  VX_LAYOUT=0 keeps the two launches.  layoutRuns: kept attempts by two launches | one (vx_layout_keep_counts).
+	bool layoutOn = false, layoutValid = false;
+	u32 layoutLevels = 0, layoutCursors[2] = { 0, 0 }, layoutTotals[MAX_LEVELS] = {};
+	uint64_t layoutRuns[2] = { 0, 0 };
 	u32 listWgs = 0;
 	void* haloBuf[4] = { nullptr, nullptr, nullptr, nullptr }; // staging of the halo messages: send below, send above, receive from below, receive from above
 	size_t haloCap[4] = { 0, 0, 0, 0 };
@@ -284,7 +294,8 @@ u32 ref_levels(u32 n)
 }
 
 void mat_store_invalidate(vx_ctx* c) { c->matStoreValid = false; }
-void slot_plan_drop(vx_ctx* c) { c->planValid = false; }
+void layout_drop(vx_ctx* c) { c->layoutValid = false; }
+void slot_plan_drop(vx_ctx* c) { c->planValid = false; layout_drop(c); } // (the layout is one of these slots' records)
 // something the material store and the slot plan depend on has changed (or is about to be freed)
 void kept_state_invalidate(vx_ctx* c) { mat_store_invalidate(c); slot_plan_drop(c); }
 
@@ -585,6 +596,7 @@ bool ensure_mat_store(vx_ctx* c)
 
 bool ensure_pools(vx_ctx* c, u32 needVerts, u32 needIdx)
 {
+	if (needVerts > c->vertCap || needIdx > c->idxCap) layout_drop(c); // (the records' offsets point into the pools that leave)
 	if (needVerts > c->vertCap) {
 		c->be.free(c->dVerts);
 		c->dVerts = c->be.alloc((size_t)needVerts * sizeof(PolyVertex));
@@ -927,6 +939,8 @@ int vx_ctx_create(int device_index, vx_ctx** out)
 	c->planOn = c->be.tune.plan != 0;
 	// VX_MAT_INPLACE=0: a run that keeps the plan still runs the store's copy items
 	c->matInPlaceOn = c->be.tune.matInPlace != 0;
+	// VX_LAYOUT=0: a run in place is still followed by k_tail
+	c->layoutOn = c->be.tune.layout != 0;
 	if (c->planOn) c->headerSet[2] = c->be.alloc((HDR_WORDS + HDR_PARTIALS) * 4);
 	if (c->planOn && !c->headerSet[2]) { vx_ctx_destroy(c); return VX_ERR_DEVICE; }
 #endif
@@ -1731,6 +1745,8 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 		bool clean = c->cleanSet >= 0;
 		ExecParams p;
 		bool planRun = false, kept = false; // this attempt may leave a slot plan behind | runs on the one that is there
+		bool layoutKept = false, oneLaunch = false; // ... is asked to keep the mesh layout as well | was launched that way
+		(void)layoutKept; (void)oneLaunch;
 #if defined(VX_BACKEND_SLOT_PLAN) && !defined(VX_CASE_DUMP)
 		// An assigning attempt or a kept one?  Kept: the plan is valid for this level count, the attempt is one of the runs that
 		// may leave one (full, single-stream, reading the cell map, timed by the device clock - what it is known to be before a set
@@ -1805,6 +1821,29 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 			if (replay) ++c->matReplayRuns[inPlace ? 1 : 0];
 		}
 #endif
+#if defined(VX_BACKEND_SLOT_PLAN) && defined(VX_BACKEND_MAT_STORE)
+		// The mesh layout: a run in place may keep it when an accepted run on these slots left it (layoutValid, set below).
+		// What it vouches for - records[slot] of every slot, listed[] and the list totals of every level, the pool cursors,
+		// and on level 0 the slots' ntBits and consBits - and who writes any of it:
+		//   * the mesh-writing bodies f0_walk, f1_block, trf_block and the general phases of tr_block, with r0_accept's,
+		//     f1_block's and trf_block's empty records, f0_next's and f0_deposit's bitmaps: inside k_main.  An attempt that keeps
+		//     the layout stores none of it; every other attempt drops the layout right here and decides anew when it is accepted;
+		//   * regular0_pass / regular_pass (k_tail's general passes, the launches of the upper capacity classes and of the levels
+		//     beyond the lattice copies), k_transition, k_regular0_fast / k_regular1_fast: attempts that are not layout-kept.  A
+		//     run that handed blocks to the general passes (HDR_SLOW) or met the large class (HDR_LARGE) leaves no layout: its
+		//     general workgroups reserve in an order of their own, and a kept run would have nobody to run them;
+		//   * list_write_pass (k_tail, k_list_write): listed[] and the totals, from the records - same attempts;
+		//   * k_dirty_head, k_main<true>, k_dirty_tail and the host's list upkeep of incremental runs: vx_polygonize_dirty drops
+		//     the plan, and slot_plan_drop drops the layout;
+		//   * vx_compact_pools, which moves the meshes and rewrites every offset, and ensure_pools when it replaces a pool: both
+		//     drop it;
+		//   * ensure_level_tables, which allocates records and lists: free_level_tables drops plan and layout;
+		//   * vx_device_block_table's upload of listed[]: only behind incremental runs (no device lists), whose plan is gone.
+		// Nothing in it depends on the material LUT: counts and offsets come from case codes, vertex reuse and the pool ranges;
+		// the LUT row only enters pack_vertex_regs, as the texture bytes of a vertex (so vx_material_lut keeps the layout).
+		layoutKept = kept && c->be.matMode == 3u && c->layoutOn && c->layoutValid && c->layoutLevels == levels;
+		if (!layoutKept) layout_drop(c);
+#endif
 		// device time: two clock words of the header on the single-stream path; the event pair on the chain of launches, with
 		// stage timing and under VX_HOST_TIMING (a recorded event is a packet of its own in the stream: ~8 us before the next kernel)
 		const bool byClock = !hostTiming && RunClock::applies(c->be, p, levels);
@@ -1833,6 +1872,19 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 #if defined(VX_CASE_DUMP)
 		for (u32 L = 0; L < levels; ++L) { c->be.fill(c->lv[L].caseDump, 0, (size_t)c->lv[L].cap * BLOCK_CELLS); c->be.fill(c->lv[L].trCaseDump, 0, (size_t)c->lv[L].cap * TR_CELLS * 2); }
 #endif
+		bool pubReady = false;
+#if defined(VX_BACKEND_SLOT_PLAN)
+		if (layoutKept) {
+			// the header travels with k_main itself: the publication is handed over in front of the launch (a run without a head
+			// has no partial sums behind its header)
+			if (!c->hdrPinned) c->hdrPinned = (u32*)c->be.alloc_pinned((HDR_WORDS + HDR_PARTIALS) * 4);
+			if (!c->hdrPinned) return fail_run(VX_ERR_DEVICE, "vx_polygonize: pinned allocation failed");
+			c->hdrPinned[HDR_PUBLISHED] = 0; // (see below)
+			pubReady = c->be.lists_publish_header(c->hdrPinned, (const u32*)c->dHeader, HDR_WORDS, (u32*)c->dHeader + HDR_PUBLISHED);
+			RunClock::tag(c->be, HDR_PUBLISHED, c->runEpoch, byClock ? (u32)HDR_CLOCK1 : 0u);
+			c->be.set_layout_end(c->layoutCursors, c->layoutTotals, (u32*)c->dHeader + HDR_LISTS);
+		}
+#endif
 		run_pipeline(c, p, levels);
 		u32 partials = 0;
 		bool published = false;
@@ -1857,13 +1909,19 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 			partials = std::min<u32>(c->be.head_partials(), (u32)HDR_PARTIALS);
 			// (the run before has published, or was waited for: nobody else writes this word now.  Its value when the header has
 			// arrived is this attempt's tag, which is not 0 and not the tag of the attempt before.)
-			c->hdrPinned[HDR_PUBLISHED] = 0;
-			published = c->be.lists_publish_header(c->hdrPinned, (const u32*)c->dHeader, HDR_WORDS + partials, (u32*)c->dHeader + HDR_PUBLISHED);
-			RunClock::tag(c->be, HDR_PUBLISHED, c->runEpoch, byClock ? (u32)HDR_CLOCK1 : 0u);
+			if (!pubReady) {
+				c->hdrPinned[HDR_PUBLISHED] = 0;
+				published = c->be.lists_publish_header(c->hdrPinned, (const u32*)c->dHeader, HDR_WORDS + partials, (u32*)c->dHeader + HDR_PUBLISHED);
+				RunClock::tag(c->be, HDR_PUBLISHED, c->runEpoch, byClock ? (u32)HDR_CLOCK1 : 0u);
+			} else
+				published = true; // (handed over in front of k_main: still the backend's to use if the launch was an ordinary one)
 			published = c->be.run_block_lists(p, plan, levels) && published;
 			c->cleanSet = c->be.tailCleaned ? (int)nextClean : (kept ? cleanKept : -1);
 #if defined(VX_BACKEND_SLOT_PLAN)
 			c->seedSet = c->be.tailSeeded ? (int)nextSeed : -1;
+			oneLaunch = c->be.layoutRan;
+			if (!oneLaunch) layout_drop(c); // (the launches of this attempt rewrite records and lists)
+			if (kept) ++c->layoutRuns[oneLaunch ? 1 : 0];
 #endif
 			c->be.stage_mark(7);
 		}
@@ -1907,12 +1965,31 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 		// a replayed block without an entry in the store (an unchanged grid has none): the store is dropped, the run repeated as a voting one
 		if (c->be.matModeUsed == 2u && c->hdr[HDR_STATS + STAT_MAT_MISS]) { mat_store_invalidate(c); c->be.matModeUsed = 0; continue; }
 #endif
+#if defined(VX_BACKEND_SLOT_PLAN)
+		// a block of a layout-kept attempt whose totals were not its record's, or one handed to the general passes (an unchanged
+		// grid has neither): the layout is dropped, the attempt repeated as an ordinary kept one, which rewrites every mesh
+		if (oneLaunch && c->hdr[HDR_STATS + STAT_LAYOUT_MISS]) { layout_drop(c); continue; }
+#endif
 		if (c->hdr[HDR_LARGE] && !c->be.largeClass) { c->be.largeClass = true; continue; } // blocks of the large class showed up: once more, with it
 #if defined(VX_BACKEND_MAT_STORE)
 		// The attempt captured: its header arrived without HDR_GIVEUP, so every material item has completed and the store is
 		// filled - whether or not the meshes fitted the pools (no material item touches them).  A repeat for larger pools
 		// replays, then, and on the slots this attempt handed out it does so in place.
 		if (c->be.matModeUsed == 1u) { c->matStoreValid = true; c->matStoreLevels = levels; }
+#endif
+#if defined(VX_BACKEND_SLOT_PLAN)
+		// An accepted attempt on the plan's slots (assigning or kept) leaves the layout behind when every record and list entry
+		// came from k_main's table-driven bodies and k_tail's list pass: the header arrived (no HDR_GIVEUP: checked above), the
+		// pools held everything, no block of the large class, nothing handed to the general passes, no empty cache.  (An attempt
+		// that kept the layout leaves it as it found it.)
+		if (!overflow && planRun && !oneLaunch) {
+			c->layoutValid = c->layoutOn && published && c->planValid && !c->hdr[HDR_LARGE] && !c->hdr[HDR_SLOW] && !c->hdr[HDR_SLOW + 1]
+			                 && !c->hdr[HDR_STATS + STAT_MAT_MISS] && levels <= (u32)PYRAMID_LEVELS
+			                 && c->vertCap < (u32)LAYOUT_MISS_OFF && c->idxCap < (u32)LAYOUT_MISS_OFF;
+			c->layoutLevels = levels;
+			c->layoutCursors[0] = usedV; c->layoutCursors[1] = usedI;
+			for (u32 L = 0; L < MAX_LEVELS; ++L) c->layoutTotals[L] = L < levels ? c->hdr[HDR_LISTS + L] : 0u;
+		}
 #endif
 		if (!overflow) break;
 		if (++retries > 3) return fail(c, VX_ERR_OVERFLOW, "vx_polygonize: output pools keep overflowing");
@@ -2027,6 +2104,7 @@ int vx_compact_pools(vx_ctx* c)
 {
 	VX_ENTER(c);
 	if (!c || !c->haveSurface) return fail(c, VX_ERR_INVALID, "vx_compact_pools: no surface");
+	layout_drop(c); // (the meshes move and every offset in records and lists with them; dropped by the call, whatever it finds to do)
 	++c->meshEpoch;
 	if (ensure_lists(c) != VX_OK) return VX_ERR_DEVICE;
 	uint64_t liveV, liveI;
@@ -2678,6 +2756,14 @@ int vx_material_inplace_counts(vx_ctx* c, uint64_t out[2])
 	VX_ENTER_RUN(c); // (host counters)
 	if (!c || !out) return fail(c, VX_ERR_INVALID, "vx_material_inplace_counts: null argument");
 	out[0] = c->matReplayRuns[0]; out[1] = c->matReplayRuns[1];
+	return VX_OK;
+}
+
+int vx_layout_keep_counts(vx_ctx* c, uint64_t out[2])
+{
+	VX_ENTER_RUN(c); // (host counters)
+	if (!c || !out) return fail(c, VX_ERR_INVALID, "vx_layout_keep_counts: null argument");
+	out[0] = c->layoutRuns[0]; out[1] = c->layoutRuns[1];
 	return VX_OK;
 }
 #endif

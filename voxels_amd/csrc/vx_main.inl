@@ -70,7 +70,63 @@ struct MainPlan {
 	// upper queue has no material segment, and regular and transition items read their slots with ordinary loads and no
 	// wait (the data is an earlier launch's).  Uniform at run time: not another instantiation of the kernel.
 	u32 matMode;
+	// 1 (only with matMode 3, in a run that keeps the slot plan): the run also keeps the MESH LAYOUT of the run before it on
+	// these slots (vx_host.inl, where layoutValid is decided) - every slot's record, the block lists and their totals and the
+	// final pool cursors are in memory already, byte for byte what this run would produce, because a block's ranges are the
+	// only thing in them that depends on the order in which blocks arrive.  So a block takes its ranges from its record
+	// (layout_ranges, vx_hip.hip) instead of reserving them, checks its totals against the record's counts, and stores
+	// neither record nor list count nor - level 0 - the slot's bitmaps; nobody builds lists behind the kernel, and its last
+	// workgroup does what is left of k_tail (LayoutEnd).  Uniform at run time, like matMode.
+	u32 layout;
 };
+
+// The end of a run that keeps the mesh layout (MainPlan::layout; pub.host == nullptr in every other run, which ends as ever):
+// the workgroup that finishes last seeds the counters of the next run that keeps the slots (k_tail's SeedRanges), puts the
+// cursors and list totals of the kept layout - the host's copies, taken from the header of the run that left it - into this
+// run's header, marks the run if a block was handed to the general passes (nobody runs them), and publishes the header to the
+// host.  Who is last is decided by a returning ticket on pub.done, drawn by every workgroup behind its own drained stores and
+// atomics: nobody waits for anybody (k_dirty_head elects its last workgroup the same way).
+struct LayoutEnd {
+	HeaderPublish pub;
+	SeedRanges seed;
+	u32* lists;             // the header's list totals
+	u32 cursors[2];         // vertices, indices
+	u32 totals[MAX_LEVELS];
+};
+
+// The kernel's arguments by their places in the kernarg segment (every instantiation has the same four).  The mirror is tied
+// to k_main's signature behind the kernel: KernargPlaces lays the parameter types of the kernel's own function type out by the
+// kernarg rule (each at the next multiple of its alignment), and a static_assert compares that with this struct's offsets -
+// an argument added, dropped or reordered there without the same change here does not compile.
+struct MainKernargs {
+	ExecParamsDev p;
+	MainPlan plan;
+	u32* clockStart;
+	LayoutEnd end;
+};
+template <typename F> struct KernargPlaces;
+template <typename... A> struct KernargPlaces<void(A...)> {
+	static constexpr size_t count = sizeof...(A);
+	static constexpr bool are(const size_t (&want)[sizeof...(A)], size_t total)
+	{
+		const size_t size[] = { sizeof(A)... }, align[] = { alignof(A)... };
+		size_t off = 0;
+		for (size_t i = 0; i < sizeof...(A); ++i) {
+			off = (off + align[i] - 1) / align[i] * align[i];
+			if (off != want[i]) return false;
+			off += size[i];
+		}
+		return off <= total;
+	}
+};
+__device__ __forceinline__ const MainKernargs& main_kernargs()
+{
+	typedef const __attribute__((address_space(4))) MainKernargs* KP;
+	KP kp = (KP)__builtin_amdgcn_kernarg_segment_ptr();
+	asm volatile("" : "+s"(kp));
+	return *(const MainKernargs*)kp;
+}
+__device__ __forceinline__ bool main_layout_kept() { return r0_uniform(main_kernargs().plan.layout) != 0u; }
 
 // DIRTY: the incremental run's form (TransVoxelRun::Execute with a Modification, src/TransVoxelImpl.cpp:429-465): the same two
 // queues over the work lists k_dirty_head wrote - level-0 blocks with the bitmaps the head formed (no SELF), material blocks
@@ -83,11 +139,12 @@ struct MainPlan {
 template <bool DIRTY, bool PARTIAL = false, bool MAP = false>
 // clockStart: a run without k_run_head (the slot plan, vx_host.inl) - workgroup 0 leaves the 100 MHz clock here as it starts, the
 // start of the run's device_ms (include/voxels_hip.h: "the first workgroup of the run"); nullptr in every other run.
-__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_main(ExecParamsDev pArg, MainPlan plan, u32* clockStart)
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_main(ExecParamsDev pArg, MainPlan plan, u32* clockStart, LayoutEnd endArg)
 {
+	(void)endArg; // (read at the end of the kernel, through main_kernargs)
 #define MAIN_PARAMS() (void)pArg; const ExecParamsDev& p = kernarg_params() // (vx_hip.hip: read afresh, per item)
 	MAIN_PARAMS();
-	if (clockStart && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(clockStart, run_clock(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (read by the publishing workgroup of k_tail, possibly on another XCD)
+	if (clockStart && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(clockStart, run_clock(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (read by the publishing workgroup - of k_tail, or the last one of this kernel - possibly on another XCD)
 	u8* tab = smem;
 	u8* state = smem + UP_TAB_LDS;
 	// (one 16-byte aligned block of statics in front of the dynamic region: its base stays aligned for the 16-byte LDS accesses)
@@ -202,6 +259,50 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) void k_
 		// (in place the segment is not part of the queue; its blocks count as replayed all the same: left in their slots)
 		if (!DIRTY && blockIdx.x == 0 && tid == 20 && matTotal) atomicAdd(&p.G.stats[STAT_MAT_PATHS + ((MAP && plan.matMode >= 2u) ? 1 : 0)], matTotal);
 	}
+	if (MAP && main_layout_kept()) { // (uniform over the launch)
+		// (everything this needs is read here, from the kernarg segment: nothing of it is carried through the kernel)
+		const MainKernargs& ka = main_kernargs();
+		const ExecParamsDev& p = ka.p;
+		const LayoutEnd& end = ka.end;
+		// this workgroup's statistics, hand-overs and mesh stores have left before it counts as finished
+#if defined(VX_CONSERVATIVE_SYNC)
+		__threadfence();
+#else
+		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+		__syncthreads();
+		if (tid0 == 0) sh.nextItem[0] = atomicAdd(end.pub.done, 1u);
+		__syncthreads();
+		if (r0_uniform(sh.nextItem[0]) + 1u == gridDim.x) { // the last workgroup of the launch
+#if defined(VX_CONSERVATIVE_SYNC)
+			__threadfence();
+#endif
+			seed_words(end.seed, (u32)tid0, (u32)WG);
+			if (tid0 == 0) {
+				__hip_atomic_store(&p.P.cursors[CUR_V], end.cursors[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				__hip_atomic_store(&p.P.cursors[CUR_I], end.cursors[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				for (u32 l = 0; l < ka.plan.levels; ++l) __hip_atomic_store(&end.lists[l], end.totals[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				// blocks handed to the general passes (a zero sample where the run before met none): nobody takes them in this run
+				if (TV_LOAD_THROUGH(p.G.slowCount) | TV_LOAD_THROUGH(p.G.slowCount + 1)) __hip_atomic_fetch_or(&p.G.stats[STAT_LAYOUT_MISS], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			}
+			// (the header words above are read back by other waves of this workgroup: publish_header_to_host loads past the caches)
+#if defined(VX_CONSERVATIVE_SYNC)
+			__threadfence();
+#else
+			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+			__syncthreads();
+			publish_header_to_host(end.pub, (u32)tid0, (u32)WG);
+		}
+	}
 }
+
+constexpr size_t MAIN_KERNARG_PLACES[] = { offsetof(MainKernargs, p), offsetof(MainKernargs, plan), offsetof(MainKernargs, clockStart), offsetof(MainKernargs, end) };
+static_assert(KernargPlaces<decltype(k_main<false, false, true>)>::count == 4 && KernargPlaces<decltype(k_main<false, false, true>)>::are(MAIN_KERNARG_PLACES, sizeof(MainKernargs))
+              && KernargPlaces<decltype(k_main<true>)>::are(MAIN_KERNARG_PLACES, sizeof(MainKernargs)) && KernargPlaces<decltype(k_main<false, true>)>::are(MAIN_KERNARG_PLACES, sizeof(MainKernargs))
+              && KernargPlaces<decltype(k_main<false>)>::are(MAIN_KERNARG_PLACES, sizeof(MainKernargs)),
+              "MainKernargs mirrors k_main's parameters: main_layout_kept and the end of the kernel read the kernarg segment through it");
+static_assert(std::is_same<decltype(k_main<false, false, true>), void(decltype(MainKernargs::p), decltype(MainKernargs::plan), decltype(MainKernargs::clockStart), decltype(MainKernargs::end))>::value,
+              "MainKernargs: a member per parameter of k_main, of the parameter's type, in the parameters' order");
 
 } // namespace

@@ -468,7 +468,7 @@ __device__ __forceinline__ R0Candidate r0_peek(const ExecParamsDev& p, const Lev
 // Does the candidate belong to this workgroup's capacity class and carry geometry?  Blocks without geometry get their
 // empty record here (the first class, lo == 0, owns them).  Uniform over the workgroup.
 template <int CAP>
-__device__ __forceinline__ bool r0_accept(const LevelDesc& L, u32 lo, const R0Candidate& c, R0Block& b)
+__device__ __forceinline__ bool r0_accept(const LevelDesc& L, u32 lo, const R0Candidate& c, R0Block& b, const bool write = true)
 {
 	// every field is taken out of its load register here, on every path: a load that is still formally pending when its
 	// register is reused later costs a full drain of the memory queue at that point
@@ -476,7 +476,7 @@ __device__ __forceinline__ bool r0_accept(const LevelDesc& L, u32 lo, const R0Ca
 	if (!valid) return false;
 	if ((lo && ntc <= lo) || ntc > (u32)CAP) return false;
 	if (ntc == 0 || skip) {
-		if (threadIdx.x == 0) reg_write_empty_record(L, slot);
+		if (threadIdx.x == 0 && write) reg_write_empty_record(L, slot); // (write == false: the slot holds it already, a run that keeps the mesh layout)
 		return false;
 	}
 	b.slot = slot; b.ntc = ntc; b.coord = coord;
