@@ -730,6 +730,85 @@ int  vx_grid_heightmap_device(vx_ctx* ctx, const vx_height_query* query, uint32_
  * it */
 int  vx_debug_height_shortcuts(vx_ctx* ctx, uint32_t enable);
 
+/* ---- ambient occlusion (HIP library only) --------------------------------------------------------------------------------
+ * One byte per vertex of a level's meshes: how open the grid is around the vertex, on the side its normal points to - 255 is
+ * fully open.  The vertex stays the reference's 48 bytes; the bytes are an array of their own, parallel to the vertex pool:
+ * byte i belongs to pool vertex i of vx_device_meshes, so a renderer binds the array as a second vertex stream with the
+ * offsets it already has.  The rule is integer arithmetic and exact: the device result is the same bytes as
+ * tests/occlusion_oracle.py, which states this text again in numpy; voxels_amd/csrc/tv_occlusion.h is the one place where the
+ * library writes it down.  Needs a context that owns a whole grid (vx_grid_upload / vx_grid_upload_packed) and has a surface.
+ *
+ * The rule.  All arithmetic is int32 unless stated otherwise.  Shifts of negative numbers are arithmetic.  Float operations are
+ * float32 with one rounding per written operation and no contraction.
+ *   Space.       s = 1 << level.  A vertex's grid-axis position is g = (pos[0], pos[2], pos[1]) and its normal is
+ *                m = (nrm[0], nrm[2], nrm[1]): mesh space is Y-up and the grid is Z-up.  A voxel is solid where its distance
+ *                sample is < 0, the definition used everywhere else.  Lattice point c of the level is grid sample c * s.  It is
+ *                air if any coordinate is < 0 or c[a] * s >= n.
+ *   Quantise.    P[a] = (int32)floorf(g[a] * (256.0f / s) + 0.5f): 24.8 fixed point in voxels of the level.
+ *                N[a] = (int32)floorf(m[a] * 127.0f + 0.5f).  A vertex with a g[a] that is not finite or has |g[a]| > 4096 is
+ *                not baked: it writes 255 and counts nowhere.  A normal component that is not finite gives N[a] = 0.  Clamp
+ *                N[a] to [-127, 127] (the clamp is applied to the floored float, so an overflowing product ends at +-127).
+ *   Directions.  There are 98 of them: the integer vectors d with max(|dx|, |dy|, |dz|) == 2, in ascending order of
+ *                ((dz + 2) * 5 + (dy + 2)) * 5 + (dx + 2).  The step vector is S[a] = floor(256 * d[a] / |d| + 0.5), written
+ *                out as a literal table.  Up to sign and permutation its entries are (256,0,0), (229,114,0), (181,181,0),
+ *                (209,105,105), (171,171,85) and (148,148,148).
+ *   Weight.      w_k = max(0, (N . S_k) >> 8).
+ *   Origin.      O = P + 2 * N: just under one voxel of the level along the normal, out of the surface.
+ *   Probe.       For a direction k with w_k > 0 and j = 1..steps, form Q = O + j * S_k and c[a] = (Q[a] + 128) >> 8.  The probe
+ *                ends unoccluded at the first c outside the grid, in the sense above.  It ends occluded at the first solid c,
+ *                with hit = j.  It ends unoccluded after `steps` air samples.
+ *   Byte.        tot = steps * sum of w_k.  occ = sum over occluded k of w_k * (steps + 1 - hit_k).
+ *                ao = tot ? 255 - (255 * occ) / tot : 255, as uint32 with integer division.
+ *
+ *   Parameters  steps = 1..VX_OCCLUSION_MAX_STEPS, the reach of a probe in voxels of the level; flags = 0 or
+ *               VX_OCCLUSION_TRANSITIONS (bake the vertices of the six transition meshes too); box_min / box_max in mesh space:
+ *               a table entry is visited by the rule of vx_scatter - its min_corner / max_corner box meets the filter box on
+ *               every axis, -INF / +INF allowed; the reserved words are zero.
+ *   Baked       the regular vertex range of every visited entry of vx_device_block_table(level), plus its six transition ranges
+ *               with the flag.  Only these bytes are written; every other byte of the array keeps its value, which is what makes
+ *               a re-bake after vx_polygonize_dirty with the edit's box (grown by the reach) as filter cheap.
+ *   Counts      vertices = vertices baked by this call, sum = the sum of their bytes, entries / visited_entries of the table,
+ *               darkest = the least byte written (255 when none), open = baked vertices whose byte is 255.  Integer sums and
+ *               maxima only (the least byte is kept as the greatest complement): nothing depends on an order or a schedule.
+ *   Scope       Meshes and tables are those of the last run, as for vx_scatter.  The grid is the grid as it is NOW: after an edit
+ *               and before the next run, the bake uses the old vertices against the new samples.
+ * vx_occlusion_device takes d_ao and d_counts (8-byte aligned, may be NULL) as device pointers, is enqueued on the context's
+ * stream (vx_set_stream) and returns without waiting: one kernel launch, and with d_counts a clear of 32 bytes before it and a
+ * launch of one lane behind it.  It allocates nothing once the working memory exists.  vx_occlusion takes host arrays and is
+ * synchronous: it bakes into a staging buffer kept with the context, pre-filled with 255, and copies the pool's n_verts bytes
+ * back, so bytes of vertices the call did not bake read 255.  capacity (in bytes = vertices) must be at least the pool's
+ * n_verts.  A level with an empty table gives VX_OK with zero counts and darkest = 255.
+ * Neither call changes the grid, the pools, the tables or any kept state: a full run afterwards is what it would have been.
+ * Everything is checked before anything is launched and nothing is written on an error: VX_ERR_INVALID for a null context, a
+ * context that does not own a whole grid (slab and attached contexts, as for the brushes), no surface, level >= the levels of
+ * the last run, null params, steps outside 1..VX_OCCLUSION_MAX_STEPS, an unknown flag bit, a non-zero reserved word, a NaN in a
+ * box, box_min > box_max on an axis, a null array, capacity < n_verts, misaligned device counts.  VX_ERR_DEVICE when working
+ * memory cannot be allocated.
+ * Working memory, kept with the context, grown when a call needs more and released with the context: 256 bytes for the counts,
+ * and for vx_occlusion one byte per pool vertex.  vx_occlusion_device with d_counts == NULL uses none. */
+#define VX_OCCLUSION_MAX_STEPS 12
+#define VX_OCCLUSION_TRANSITIONS 1u      /* flags: bake the six transition meshes' vertices too */
+typedef struct vx_occlusion_params {     /* 48 bytes */
+    uint32_t steps;                      /* 1..VX_OCCLUSION_MAX_STEPS: reach of a probe, in voxels of the level */
+    uint32_t flags;
+    float    box_min[3], box_max[3];     /* mesh space; an entry is visited by the rule of vx_scatter ("visited"); -INF/+INF allowed */
+    uint32_t reserved[4];                /* 0 */
+} vx_occlusion_params;
+typedef struct vx_occlusion_counts {     /* 32 bytes */
+    uint64_t vertices;                   /* vertices baked by this call */
+    uint64_t sum;                        /* sum of their bytes */
+    uint32_t entries, visited_entries;
+    uint32_t darkest;                    /* least byte written, 255 when none */
+    uint32_t open;                       /* baked vertices whose byte is 255 */
+} vx_occlusion_counts;
+int  vx_occlusion_device(vx_ctx* ctx, uint32_t level, const vx_occlusion_params* params /* host */,
+                         uint8_t* d_ao /* device */, uint64_t capacity, vx_occlusion_counts* d_counts /* device, may be NULL */);
+int  vx_occlusion(vx_ctx* ctx, uint32_t level, const vx_occlusion_params* params,
+                  uint8_t* ao /* host */, uint64_t capacity, vx_occlusion_counts* counts /* host, may be NULL */);
+/* tests: whether the per-block sign summaries may stand in for distance rows (the default: yes); nothing of a result depends on
+ * it */
+int  vx_debug_occlusion_shortcuts(vx_ctx* ctx, uint32_t enable);
+
 /* MaterialMap::GetMaterial resolved on the host (include/MaterialMap.h:19-30): lut[id] = {DiffuseIds0[3],
  * DiffuseIds1[3]}, valid[id] == 0 means GetMaterial returned NULL (texture bytes stay 0). */
 int vx_material_lut(vx_ctx* ctx, const uint8_t* lut /*256*6*/, const uint8_t* valid /*256*/);

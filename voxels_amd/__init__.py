@@ -14,7 +14,8 @@ from .binding import (BLOCK_INFO_DTYPE, BOX_DTYPE, DRAW_INDEXED_DTYPE, HIT_DTYPE
                       PASTE_COUNTS_DTYPE, PASTE_DTYPE, PASTE_MAX_COUNT, PASTE_MAX_STAMPS, PASTE_PAINT, PASTE_REPLACE, PASTE_RESULT_DTYPE, PASTE_SUBTRACT, PASTE_UNION,
                       STAMP_INFO_DTYPE, STAMP_MAX_EDGE, STAMP_MAX_VOXELS, Stamp, paste_boxes, pastes,
                       MEASURE_DTYPE, MEASURE_MAX_BOXES, RECORD_DELTA_DTYPE,
-                      HEIGHT_COUNTS_DTYPE, HEIGHT_COUNT_SURFACES, HEIGHT_FROM_BOTTOM, HEIGHT_FROM_TOP, HEIGHT_MAX_LAYERS, HEIGHT_NONE, HEIGHT_QUERY_DTYPE, height_query)
+                      HEIGHT_COUNTS_DTYPE, HEIGHT_COUNT_SURFACES, HEIGHT_FROM_BOTTOM, HEIGHT_FROM_TOP, HEIGHT_MAX_LAYERS, HEIGHT_NONE, HEIGHT_QUERY_DTYPE, height_query,
+                      OCCLUSION_COUNTS_DTYPE, OCCLUSION_MAX_STEPS, OCCLUSION_PARAMS_DTYPE, OCCLUSION_TRANSITIONS, occlusion_params)
 
 __all__ = ["BLOCK_INFO_DTYPE", "BOX_DTYPE", "DRAW_INDEXED_DTYPE", "HIT_DTYPE", "LOD_COUNTS_DTYPE", "LOD_DRAW_DTYPE", "POINT_HIT_DTYPE", "POINT_QUERY_DTYPE",
            "RAY_DTYPE", "SCATTER_COUNTS_DTYPE", "SCATTER_PARAMS_DTYPE", "SCATTER_POINT_DTYPE", "SCATTER_RANGE_DTYPE", "SPHERE_CAST_DTYPE", "SPHERE_HIT_DTYPE", "VERTEX_DTYPE",
@@ -25,4 +26,5 @@ __all__ = ["BLOCK_INFO_DTYPE", "BOX_DTYPE", "DRAW_INDEXED_DTYPE", "HIT_DTYPE", "
            "STAMP_INFO_DTYPE", "PASTE_DTYPE", "PASTE_RESULT_DTYPE", "PASTE_COUNTS_DTYPE", "STAMP_MAX_EDGE", "STAMP_MAX_VOXELS", "PASTE_MAX_COUNT", "PASTE_MAX_STAMPS",
            "PASTE_REPLACE", "PASTE_UNION", "PASTE_SUBTRACT", "PASTE_PAINT", "Stamp", "paste_boxes", "pastes",
            "MEASURE_DTYPE", "RECORD_DELTA_DTYPE", "MEASURE_MAX_BOXES",
-           "HEIGHT_QUERY_DTYPE", "HEIGHT_COUNTS_DTYPE", "HEIGHT_MAX_LAYERS", "HEIGHT_NONE", "HEIGHT_FROM_TOP", "HEIGHT_FROM_BOTTOM", "HEIGHT_COUNT_SURFACES", "height_query"]
+           "HEIGHT_QUERY_DTYPE", "HEIGHT_COUNTS_DTYPE", "HEIGHT_MAX_LAYERS", "HEIGHT_NONE", "HEIGHT_FROM_TOP", "HEIGHT_FROM_BOTTOM", "HEIGHT_COUNT_SURFACES", "height_query",
+           "OCCLUSION_PARAMS_DTYPE", "OCCLUSION_COUNTS_DTYPE", "OCCLUSION_MAX_STEPS", "OCCLUSION_TRANSITIONS", "occlusion_params"]

@@ -91,6 +91,11 @@ HEIGHT_COUNTS_DTYPE = np.dtype([("columns", "<u8"), ("covered", "<u8"), ("surfac
 assert HEIGHT_QUERY_DTYPE.itemsize == 48 and HEIGHT_COUNTS_DTYPE.itemsize == 48
 HEIGHT_MAX_LAYERS, HEIGHT_NONE = 8, 0xFFFFFFFF
 HEIGHT_FROM_TOP, HEIGHT_FROM_BOTTOM, HEIGHT_COUNT_SURFACES = 0, 1, 1
+# ambient occlusion (include/voxels_hip.h, "ambient occlusion")
+OCCLUSION_PARAMS_DTYPE = np.dtype([("steps", "<u4"), ("flags", "<u4"), ("box_min", "<f4", 3), ("box_max", "<f4", 3), ("reserved", "<u4", 4)])
+OCCLUSION_COUNTS_DTYPE = np.dtype([("vertices", "<u8"), ("sum", "<u8"), ("entries", "<u4"), ("visited_entries", "<u4"), ("darkest", "<u4"), ("open", "<u4")])
+assert OCCLUSION_PARAMS_DTYPE.itemsize == 48 and OCCLUSION_COUNTS_DTYPE.itemsize == 32
+OCCLUSION_MAX_STEPS, OCCLUSION_TRANSITIONS = 12, 1
 SPHERE_STARTED_IN_CONTACT = 1
 # vx_lod_params / vx_lod_draw / vx_draw_indexed / vx_lod_counts (include/voxels_hip.h, LOD selection)
 LOD_PARAMS_DTYPE = np.dtype([("camera", "<f4", 3), ("n_planes", "<u4"), ("planes", "<f4", (6, 4)), ("ranges", "<f4", 16)])
@@ -399,6 +404,15 @@ class HipLibrary:
             lib.vx_debug_height_shortcuts.argtypes = [vp, u32]
             for name in height_calls:
                 getattr(lib, name).restype = C.c_int
+        # ambient occlusion: HIP builds only, likewise
+        occlusion_calls = ("vx_occlusion", "vx_occlusion_device", "vx_debug_occlusion_shortcuts")
+        self.has_occlusion = all(hasattr(lib, name) for name in occlusion_calls)
+        if self.has_occlusion:
+            lib.vx_occlusion.argtypes = [vp, u32, vp, vp, C.c_uint64, vp]
+            lib.vx_occlusion_device.argtypes = [vp, u32, vp, vp, C.c_uint64, vp]
+            lib.vx_debug_occlusion_shortcuts.argtypes = [vp, u32]
+            for name in occlusion_calls:
+                getattr(lib, name).restype = C.c_int
         self.has_lod = hasattr(lib, "vx_lod_select")
         if self.has_lod:
             lib.vx_lod_select_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
@@ -441,6 +455,16 @@ def height_query(box, direction="top", layers=1, count_surfaces=False):
     q["layers"] = layers
     q["flags"] = HEIGHT_COUNT_SURFACES if count_surfaces else 0
     return q
+
+
+def occlusion_params(steps=8, transitions=False, box_min=None, box_max=None):
+    """one OCCLUSION_PARAMS_DTYPE record; the filter box in mesh space (Y up), None = unbounded"""
+    prm = np.zeros(1, OCCLUSION_PARAMS_DTYPE)
+    prm["steps"] = steps
+    prm["flags"] = OCCLUSION_TRANSITIONS if transitions else 0
+    prm["box_min"] = -np.inf if box_min is None else np.asarray(box_min, np.float32)
+    prm["box_max"] = np.inf if box_max is None else np.asarray(box_max, np.float32)
+    return prm
 
 
 def walk_query(box=None, clearance=2, step_up=1, step_down=1, cost_axial=10, cost_diagonal=14, cost_climb=0, max_cost=1 << 30):
@@ -843,6 +867,40 @@ class Polygonizer:
         self._check(self._lib.vx_grid_heightmap_device(self._h, _ptr(q), address(heights, 4, cells * int(layers)), address(materials, 1, cells * int(layers)),
                                                        address(surfaces, 2, cells), _ptr(rec)), "vx_grid_heightmap_device")
         return rec[0] if counts else None
+
+    def _occlusion_lib(self):
+        if not self._L.has_occlusion:
+            raise VoxelsHipError("%s has no ambient occlusion (vx_occlusion*)" % self._L.path)
+        return self._L.lib
+
+    def occlusion(self, level, params=None, counts=True):
+        """vx_occlusion: an OCCLUSION_PARAMS_DTYPE record (occlusion_params(), the default when None) -> (uint8 array parallel to
+        the vertex pool of device_meshes(), 255 where the call baked nothing; the OCCLUSION_COUNTS_DTYPE record, or None)"""
+        lib = self._occlusion_lib()
+        prm = np.ascontiguousarray(occlusion_params() if params is None else params, OCCLUSION_PARAMS_DTYPE)
+        nv = int(self.device_meshes()[2])
+        ao = np.zeros(nv, np.uint8)
+        rec = np.zeros(1, OCCLUSION_COUNTS_DTYPE) if counts else None
+        self._check(lib.vx_occlusion(self._h, int(level), _ptr(prm), C.c_void_p(ao.ctypes.data if nv else None), nv, _ptr(rec)), "vx_occlusion")
+        return ao, (rec[0] if counts else None)
+
+    def occlusion_device(self, level, params, d_ao, capacity=None, d_counts=None):
+        """vx_occlusion_device: d_ao (uint8, at least the pool's n_verts entries) and d_counts (32 bytes, 8-byte aligned, or None) are
+        torch device tensors or device addresses (ints; then give the capacity); queued on the context's stream (set_stream),
+        returns without waiting."""
+        lib = self._occlusion_lib()
+        prm = np.ascontiguousarray(params, OCCLUSION_PARAMS_DTYPE)
+
+        def address(a):
+            return C.c_void_p(a if a is None or isinstance(a, int) else a.data_ptr())
+
+        if capacity is None:
+            assert not isinstance(d_ao, int) and d_ao.is_cuda and d_ao.is_contiguous() and d_ao.element_size() == 1
+            capacity = d_ao.numel()
+        self._check(lib.vx_occlusion_device(self._h, int(level), _ptr(prm), address(d_ao), int(capacity), address(d_counts)), "vx_occlusion_device")
+
+    def debug_occlusion_shortcuts(self, enable):
+        self._check(self._occlusion_lib().vx_debug_occlusion_shortcuts(self._h, 1 if enable else 0), "vx_debug_occlusion_shortcuts")
 
     def capture_stamp(self, box):
         """vx_stamp_capture: the voxels of box = (lo, hi) in grid coordinates (internal axes, Z up) -> a Stamp"""

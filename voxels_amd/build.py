@@ -61,7 +61,7 @@ GXX_TARGETS = {
     "walk_host": ("tests/walk/libvoxels_walk_host.so", ["tests/walk/walk_host.cpp"], [], [], []),
     "undo_host": ("tests/undo/libvoxels_undo_host.so", ["tests/undo/undo_host.cpp"], ["-ffp-contract=off"], [], []),
     "stamp_host": ("tests/stamp/libvoxels_stamp_host.so", ["tests/stamp/stamp_host.cpp"], ["-ffp-contract=off"], [], []),
-    "measure_host": ("tests/measure/libvoxels_measure_host.so", ["tests/measure/measure_host.cpp", "tests/height/height_host.cpp"], ["-ffp-contract=off"], [], []),
+    "measure_host": ("tests/measure/libvoxels_measure_host.so", ["tests/measure/measure_host.cpp", "tests/height/height_host.cpp", "tests/occlusion/occlusion_host.cpp"], ["-ffp-contract=off"], [], []),
     "smooth_host": ("tests/smooth/libvoxels_smooth_host.so", ["tests/smooth/smooth_host.cpp"], ["-ffp-contract=off", "-Wno-unknown-pragmas"], [], []),
     "scatter_host": ("tests/scatter/libvoxels_scatter_host.so", ["tests/scatter/scatter_host.cpp"], ["-ffp-contract=off", "-Wno-unknown-pragmas"], [], []),
     "overlap_host": ("tests/overlap/libvoxels_overlap_host.so", ["tests/overlap/overlap_host.cpp"], ["-ffp-contract=off", "-Wno-unknown-pragmas"], [], []),
@@ -154,7 +154,8 @@ def build_hip(force=False, verbose=True):
                            "k_rec_mark", "k_rec_scan", "k_rec_list", "k_rec_capture", "k_rec_diff", "k_rec_pack", "k_rec_swap",
                            "k_stamp_capture", "k_paste_count", "k_paste_fill", "k_paste_apply",
                            "k_measure_pairs", "k_measure_finish", "k_rec_measure",
-                           "k_height_tiles")
+                           "k_height_tiles",
+                           "k_occlusion_bake", "k_occlusion_counts")
                if not any(k in name and "ScratchSize" in v for name, v in table.items())]
     if missing:
         os.remove(out)
@@ -316,7 +317,12 @@ def build_measure_host(force=False):
     the header's structs - tests only (tests/test_measure.py, tests/test_abi_measure.py).  The same library holds the host side of
     the tests of the height maps, which walk the same rows (tests/height/height_host.cpp): csrc/tv_height.h in a plain loop over
     columns, and the kernel's tile pipeline (row masks, column bits, the carry, the early exit, sign summaries given or withheld)
-    run on the CPU, the entry checks and the layout of the header's structs (tests/test_height.py, tests/test_abi_height.py)."""
+    run on the CPU, the entry checks and the layout of the header's structs (tests/test_height.py, tests/test_abi_height.py).  And
+    the host side of the tests of vx_occlusion, whose staging reads the same 16-byte rows and sign summaries
+    (tests/occlusion/occlusion_host.cpp): the rule of csrc/tv_occlusion.h in a plain loop over vertices and the dense grid, and the
+    kernel's pipeline - staged row masks of a block's neighbourhood, then the probes, with the region's reach as a parameter so that
+    the reads from the grid itself are reached - the entry checks and the layout of the header's structs (tests/test_occlusion.py,
+    tests/test_abi_occlusion.py)."""
     return _build_shared("measure_host", force)
 
 

@@ -4446,3 +4446,4 @@ struct Backend {
 #include "vx_scatter.inl"
 #include "vx_overlap.inl"
 #include "vx_height.inl"
+#include "vx_occlusion.inl"

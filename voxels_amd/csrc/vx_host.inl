@@ -49,7 +49,7 @@ typedef ListedBlock EmittedBlock;
 enum { VX_MAX_GRID = 2048 };
 // The query and edit modules (vx_<name>.inl), in the order vx_ctx_destroy drops their states.  A slot holds what one module
 // keeps between calls; this file knows no module's type (module_state below).
-enum ModuleId { MOD_RAY, MOD_LOD, MOD_BRUSH, MOD_ISLAND, MOD_SMOOTH, MOD_SCATTER, MOD_WALK, MOD_UNDO, MOD_OVERLAP, MOD_STAMP, MOD_MEASURE, MOD_HEIGHT, MOD_COUNT };
+enum ModuleId { MOD_RAY, MOD_LOD, MOD_BRUSH, MOD_ISLAND, MOD_SMOOTH, MOD_SCATTER, MOD_WALK, MOD_UNDO, MOD_OVERLAP, MOD_STAMP, MOD_MEASURE, MOD_HEIGHT, MOD_OCCLUSION, MOD_COUNT };
 struct ModuleSlot {
 	void* state;
 	void (*drop)(vx_ctx*, void*);
