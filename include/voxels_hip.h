@@ -847,8 +847,11 @@ int vx_level_counts(vx_ctx* ctx, uint32_t level, uint32_t* n_blocks, uint64_t to
 int vx_download_level(vx_ctx* ctx, uint32_t level, vx_block_info* infos, vx_vertex* verts, uint32_t* idx,
                       vx_vertex* tverts, uint32_t* tidx);
 /* Device-resident hand-off (renderer interop): the meshes stay in two device pools; a block's meshes are contiguous
- * ranges of them.  A full run rewrites the pools; an incremental run appends the rebuilt blocks behind what is there
- * (ranges of kept blocks stay valid, ranges of replaced blocks become garbage until the next full run).  d_verts /
+ * ranges of them.  A full run that hands out pool ranges rewrites both pools; a full run that keeps the mesh layout
+ * (vx_layout_keep_counts out[1]) rewrites every vertex where it was and leaves the index pool's bytes alone
+ * (vx_index_keep_counts) - they are what it would store; an incremental run appends the rebuilt blocks behind what is there
+ * (ranges of kept blocks stay valid, ranges of replaced blocks become garbage until the next full run).  The pools are
+ * read-only for the caller, as the const pointers say: a kept run relies on the index bytes it finds.  d_verts /
  * d_indices are valid until the next run on this context (an incremental run may move the pools when it has to grow
  * them); indices are relative to the start of their own mesh, exactly as downloaded. */
 typedef struct vx_block_ranges {
@@ -1254,7 +1257,8 @@ int vx_slot_plan_counts(vx_ctx* ctx, uint64_t out[2]);
  * launches: out[0] = two, k_main and k_tail, out[1] = one, k_main alone - a run in place (vx_material_inplace_counts out[1]) on
  * slots whose last accepted run left its mesh layout behind: every block's record, the block lists with their totals and the
  * pool cursors, which depend on the grid, the BF_Empty flags, the level count and the slot plan alone (not on the material
- * table: vx_material_lut keeps the layout).  Such a run writes every mesh where its record says it was, rebuilds no list, and
+ * table: vx_material_lut keeps the layout).  Such a run rewrites every vertex where its record says it was, leaves the index
+ * pool's bytes alone (vx_index_keep_counts; the pools are read-only for the caller), rebuilds no list, and
  * its last workgroup publishes the header.  Whatever drops the slot plan drops the layout, and so do vx_compact_pools, pools
  * that had to grow, and a run that handed a block to the general passes or met the large capacity class.
  * VX_LAYOUT=0 (read at context creation) keeps no layout: every kept run is two launches.
@@ -1262,6 +1266,17 @@ int vx_slot_plan_counts(vx_ctx* ctx, uint64_t out[2]);
  * (vx_level_ranges) are not: a run of two launches reserves them anew, in the order its blocks arrive, while a run of one launch
  * writes every mesh where the run before left it - so with the layout kept the offsets stay the same from run to run.  HIP builds only. */
 int vx_layout_keep_counts(vx_ctx* ctx, uint64_t out[2]);
+
+/* Full-run attempts of this context that kept the mesh layout (vx_layout_keep_counts out[1], since the context was created) by
+ * what they did with the index pool: out[0] = rewrote every index, out[1] = kept the indices - the pool already holds, byte for
+ * byte, what the run would store: an index is a vertex base of the kept layout plus an ordinal that follows from the signs and
+ * material ids of the unchanged grid, and nothing in it depends on the material table.  Such a run computes and stores every
+ * vertex as always (the texture bytes of a vertex do depend on the table), checks every block's index count against its record,
+ * and neither forms nor stores the indices of the table-driven blocks; a transition block with an exact zero on a staged plane
+ * still writes its (unchanged) indices.  Whatever drops the layout ends it: the next run rewrites the pool.
+ * VX_KEEP_INDICES=0 (read at context creation): every run that keeps the layout rewrites the indices.
+ * Diagnostics: pool contents, block tables, statistics and vx_exec_info are the same either way.  HIP builds only. */
+int vx_index_keep_counts(vx_ctx* ctx, uint64_t out[2]);
 
 /* The device forms of the exactness-critical arithmetic checked exhaustively on the GPU they run on (the reference does
  * this arithmetic on the host: t = (v1 << 8) / (v1 - v0), src/TransVoxelImpl.cpp:1591; normalizeFixZero, :93-103):

@@ -184,8 +184,9 @@ template <typename ST>
 TV_HD u32 f0_cell(ST& st, const F0Tables& T, u32 k, u32* classCount) { return fx_cell<F0Layout>(st, T, k, classCount); }
 
 // descriptors of cell k's new vertices and triangles that fall into the given chunks; base = vertex base | triangle base << 16
+// tris == false (uniform; a run that keeps the index pool, MainPlan::layout 2): nobody reads a triangle descriptor - none is written
 template <typename ST>
-TV_HD void f0_describe(ST& st, const F0Tables& T, u32 k, u32 base, u32 chunkV, u32 chunkT)
+TV_HD void f0_describe(ST& st, const F0Tables& T, u32 k, u32 base, u32 chunkV, u32 chunkT, const bool tris = true)
 {
 	const u32 F0_VDESC = (u32)(sizeof(st.vdesc) / sizeof(st.vdesc[0])), F0_TDESC = (u32)(sizeof(st.tdesc) / sizeof(st.tdesc[0])); // (shadow the level-0 capacities)
 	const u32 a = st.cellAN[k][0];
@@ -201,6 +202,7 @@ TV_HD void f0_describe(ST& st, const F0Tables& T, u32 k, u32 base, u32 chunkV, u
 			++j;
 		}
 	}
+	if (!tris) return;
 	const u32 ntri = (a >> 24) & 7u;
 	u32 t = base >> 16;
 	if (t < chunkT + F0_TDESC && t + 5 > chunkT) {

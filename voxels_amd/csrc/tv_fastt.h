@@ -134,7 +134,8 @@ TV_HD u32 trf_cell(TrState& st, const TrfRow* rows, u32 k, u32 mat, u32 matCol, 
 }
 
 // descriptors of cell k's new vertices and triangles that fall into the given chunks (vbase / ibase scanned)
-TV_HD void trf_describe(TrState& st, const Tables& T, u32 k, u32 chunkV, u32 chunkT)
+// tris == false (uniform; a run that keeps the index pool, MainPlan::layout 2): no triangle descriptor is written (f0_describe)
+TV_HD void trf_describe(TrState& st, const Tables& T, u32 k, u32 chunkV, u32 chunkT, const bool tris = true)
 {
 	u32 m = st.newMask[k];
 	u32 j = st.vbase[k];
@@ -146,6 +147,7 @@ TV_HD void trf_describe(TrState& st, const Tables& T, u32 k, u32 chunkV, u32 chu
 			++j;
 		}
 	}
+	if (!tris) return;
 	const u32 ntri = (u32)T.trCell((st.cellBits[k] >> 9) & 0x7Fu)[0] & 15u;
 	u32 t = (u32)st.ibase[k] / 3u; // (index counts are multiples of three, and so are their prefix sums)
 	if (t < chunkT + (u32)TRF_TDESC && t + 12 > chunkT) {

@@ -360,12 +360,13 @@ __device__ __forceinline__ void f0_walk(const F0Tables& T, Fast0State<CAP>& st, 
 					if (MAP && main_layout_kept()) layout_ranges(p, L.records[cur.slot], vTotal, tTotal * 3u, st.vOff, st.iOff);
 					else reserve_both(p.P.cursors, vTotal, tTotal * 3u, st.vOff, st.iOff);
 				}
+				const bool tris = !(MAP && main_indices_kept()); // (the index pool is kept: no triangle descriptors)
 				for (u32 k0 = kBeg; k0 < kEnd; k0 += 64u) {
 					const u32 k = k0 + lane;
 					if (k < kEnd) {
 						const u32 base = st.cellC[k] + waveBase;
 						st.cellC[k] = base;
-						f0_describe(st, T, k, base, 0u, 0u);
+						f0_describe(st, T, k, base, 0u, 0u, tris);
 					}
 				}
 			}
@@ -376,16 +377,18 @@ __device__ __forceinline__ void f0_walk(const F0Tables& T, Fast0State<CAP>& st, 
 			const bool room = r0_uniform(st.vOff) + vTotalU <= p.P.vertCap && r0_uniform(st.iOff) + tTotalU * 3u <= p.P.idxCap;
 			// Vertices and indices leave in ONE loop, and the next block's inputs are requested inside its first trip (a loop
 			// with stores that is entered while loads are in flight makes the compiler drain the memory queue in front of it).
+			// Where the run keeps the index pool (MainPlan::layout 2, read where it decides: main_indices_kept) the pool holds this
+			// block's indices byte for byte: no chunk is there for the triangles' sake, none describes them, and tEnd is 0.
 			if (room) {
-				for (u32 chunk = 0; chunk == 0 || chunk * F0_VDESC < vTotalU || chunk * F0_TDESC < tTotalU; ++chunk) {
+				for (u32 chunk = 0; chunk == 0 || chunk * F0_VDESC < vTotalU || (chunk * F0_TDESC < tTotalU && !(MAP && main_indices_kept())); ++chunk) {
 					const u32 cv = chunk * F0_VDESC, ct = chunk * F0_TDESC;
 					if (chunk) {
 						__syncthreads();
-						for (u32 k = (u32)tid; k < nt; k += WG) f0_describe(st, T, k, st.cellC[k], cv, ct);
+						for (u32 k = (u32)tid; k < nt; k += WG) f0_describe(st, T, k, st.cellC[k], cv, ct, !(MAP && main_indices_kept()));
 						__syncthreads();
 					}
 					const u32 vEnd = cv < vTotalU ? min(vTotalU - cv, (u32)F0_VDESC) : 0u;
-					const u32 tEnd = ct < tTotalU ? min(tTotalU - ct, (u32)F0_TDESC) : 0u;
+					const u32 tEnd = (ct < tTotalU && !(MAP && main_indices_kept())) ? min(tTotalU - ct, (u32)F0_TDESC) : 0u;
 					PolyVertex* vOut = p.P.verts + r0_uniform(st.vOff) + cv;
 					u32* iOut = p.P.idx + r0_uniform(st.iOff) + ct * 3u;
 					for (u32 base = 0; base < vEnd || base < tEnd; base += WG) {

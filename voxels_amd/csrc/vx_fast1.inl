@@ -195,12 +195,13 @@ __device__ __forceinline__ void f1_block(const ExecParamsDev& p, const F0Tables&
 			if (GATED && main_layout_kept()) layout_ranges(p, L.records[slot], vTotal, tTotal * 3u, st.vOff, st.iOff);
 			else reserve_both(p.P.cursors, vTotal, tTotal * 3u, st.vOff, st.iOff);
 		}
+		const bool tris = !(GATED && main_indices_kept()); // (the index pool is kept: no triangle descriptors, see f0_walk)
 		for (u32 k0 = kBeg; k0 < kEnd; k0 += 64u) {
 			const u32 k = k0 + lane;
 			if (k < kEnd) {
 				const u32 base = st.cellC[k] + waveBase;
 				st.cellC[k] = base;
-				f0_describe(st, T, k, base, 0u, 0u);
+				f0_describe(st, T, k, base, 0u, 0u, tris);
 			}
 		}
 	}
@@ -211,15 +212,15 @@ __device__ __forceinline__ void f1_block(const ExecParamsDev& p, const F0Tables&
 	const int ox = (int)(bx * 16 * L.mult), oy = (int)(by * 16 * L.mult), oz = (int)(bz * 16 * L.mult);
 	if (room) {
 		u32 notInterior = 0;
-		for (u32 chunk = 0; chunk == 0 || chunk * F1_VDESC < vTotalU || chunk * F1_TDESC < tTotalU; ++chunk) {
+		for (u32 chunk = 0; chunk == 0 || chunk * F1_VDESC < vTotalU || (chunk * F1_TDESC < tTotalU && !(GATED && main_indices_kept())); ++chunk) {
 			const u32 cv = chunk * F1_VDESC, ct = chunk * F1_TDESC;
 			if (chunk) {
 				__syncthreads();
-				for (u32 k = (u32)tid; k < nt; k += WG) f0_describe(st, T, k, st.cellC[k], cv, ct);
+				for (u32 k = (u32)tid; k < nt; k += WG) f0_describe(st, T, k, st.cellC[k], cv, ct, !(GATED && main_indices_kept()));
 				__syncthreads();
 			}
 			const u32 vEnd = cv < vTotalU ? min(vTotalU - cv, (u32)F1_VDESC) : 0u;
-			const u32 tEnd = ct < tTotalU ? min(tTotalU - ct, (u32)F1_TDESC) : 0u;
+			const u32 tEnd = (ct < tTotalU && !(GATED && main_indices_kept())) ? min(tTotalU - ct, (u32)F1_TDESC) : 0u; // (the index pool is kept: no triangles, see f0_walk)
 			PolyVertex* vOut = p.P.verts + r0_uniform(st.vOff) + cv;
 			u32* iOut = p.P.idx + r0_uniform(st.iOff) + ct * 3u;
 			for (u32 base = 0; base < vEnd || base < tEnd; base += WG) {

@@ -110,30 +110,32 @@ __device__ __forceinline__ bool trf_block(const ExecParamsDev& p, const RegBlock
 			if (GATED && main_layout_kept()) layout_ranges_faces(p, L.records[b.slot], 0, 6, tot & 0xFFFFu, tot >> 16, st.vOff, st.iOff);
 			else reserve_both(p.P.cursors, tot & 0xFFFFu, tot >> 16, st.vOff, st.iOff);
 		}
+		const bool tris = !(GATED && main_indices_kept()); // (the index pool is kept: no triangle descriptors, see f0_walk)
 		for (u32 k0 = kBeg; k0 < kEnd; k0 += 64u) {
 			const u32 k = k0 + lane;
 			if (k < kEnd) {
 				st.vbase[k] = (u16)((u32)st.vbase[k] + (waveBase & 0xFFFFu));
 				st.ibase[k] = (u16)((u32)st.ibase[k] + (waveBase >> 16));
-				trf_describe(st, T, k, 0u, 0u);
+				trf_describe(st, T, k, 0u, 0u, tris);
 			}
 		}
 	}
 	__syncthreads();
 
 	// ---- one lane = one vertex and one triangle ----------------------------------------------------------------------------
+	// (the index pool is kept, MainPlan::layout 2, read where it decides: no chunk for the triangles' sake, none described, tEnd 0)
 	const u32 vTotal = r0_uniform(st.vTotal), iTotal = r0_uniform(st.iTotal), tTotal = iTotal / 3u;
 	const u32 vOff = r0_uniform(st.vOff), iOff = r0_uniform(st.iOff);
 	if (vOff + vTotal <= p.P.vertCap && iOff + iTotal <= p.P.idxCap) {
-		for (u32 chunk = 0; chunk == 0 || chunk * VDESC_CAP < vTotal || chunk * TRF_TDESC < tTotal; ++chunk) {
+		for (u32 chunk = 0; chunk == 0 || chunk * VDESC_CAP < vTotal || (chunk * TRF_TDESC < tTotal && !(GATED && main_indices_kept())); ++chunk) {
 			const u32 cv = chunk * VDESC_CAP, ct = chunk * TRF_TDESC;
 			if (chunk) {
 				__syncthreads();
-				for (u32 k = (u32)tid; k < nt; k += WG) trf_describe(st, T, k, cv, ct);
+				for (u32 k = (u32)tid; k < nt; k += WG) trf_describe(st, T, k, cv, ct, !(GATED && main_indices_kept()));
 				__syncthreads();
 			}
 			const u32 vEnd = cv < vTotal ? min(vTotal - cv, (u32)VDESC_CAP) : 0u;
-			const u32 tEnd = ct < tTotal ? min(tTotal - ct, (u32)TRF_TDESC) : 0u;
+			const u32 tEnd = (ct < tTotal && !(GATED && main_indices_kept())) ? min(tTotal - ct, (u32)TRF_TDESC) : 0u;
 			PolyVertex* vOut = p.P.verts + vOff + cv;
 			u32* iOut = p.P.idx + iOff + ct * 3u;
 			for (u32 base = 0; base < vEnd || base < tEnd; base += WG) {

@@ -87,8 +87,11 @@ __device__ __forceinline__ const ExecParamsDev& kernarg_params()
 // k_main only (its per-block bodies, under the template arguments no other kernel passes): MainPlan::layout of the running
 // launch - 1: the run keeps the mesh layout - read afresh from the kernarg segment wherever it decides something, like the
 // parameters above: a flag carried through a block's phases would be one more scalar register in bodies that have none to spare.
+// main_indices_kept: 2 - the run keeps the index pool's bytes as well: the table-driven bodies write no triangle descriptor and
+// no index.  Read the same way, right where the descriptors or the emit loop's bounds are formed.
 // (Defined in vx_main.inl, behind MainPlan.)
 __device__ __forceinline__ bool main_layout_kept();
+__device__ __forceinline__ bool main_indices_kept();
 
 constexpr int WG = 256;
 constexpr int REG_CAP_SMALL = LARGE_THRESHOLD; // LDS capacity class of the regular pass that covers ordinary surfaces
@@ -3413,6 +3416,7 @@ struct Backend {
 		u32 plan = 1;        // VX_PLAN=0: no slot plan - every full run launches k_run_head
 		u32 matInPlace = 1;  // VX_MAT_INPLACE=0: a run that keeps the slot plan still copies the material caches from the store into their slots
 		u32 layout = 1;      // VX_LAYOUT=0: a run in place still reserves its pool ranges and is followed by k_tail (two launches, not one)
+		u32 keepIndices = 1; // VX_KEEP_INDICES=0: a run that keeps the mesh layout still rewrites the index pool (MainPlan::layout 1, not 2)
 		// fixed since round 6 (were environment variables while they were being measured; profiles/HISTORY.md has the sweeps)
 		static constexpr u32 classifyRowGroup = 4, regWgsPerCu = 20, f1WgsPerCu = 20, foldBlocks = 65536, upWgsPerCu = 5, mainWgsPerCu = 4, mainBatch = 2, mainUpperNum = 1, mainUpperDen = 4;
 		bool fast0() const { return (fast & 1u) != 0; }
@@ -3451,6 +3455,7 @@ struct Backend {
 		tune.plan = env_u32("VX_PLAN", 1);
 		tune.matInPlace = env_u32("VX_MAT_INPLACE", 1);
 		tune.layout = env_u32("VX_LAYOUT", 1);
+		tune.keepIndices = env_u32("VX_KEEP_INDICES", 1);
 		hipDeviceProp_t prop;
 		if (hipGetDeviceProperties(&prop, device) == hipSuccess) cus = prop.multiProcessorCount;
 		if (!check(hipStreamCreateWithFlags(&ownStream, hipStreamNonBlocking), "hipStreamCreate")) { err = lastError; return false; }
@@ -3794,11 +3799,13 @@ struct Backend {
 	bool keepSlots = false;
 	// ... and whether it may also keep the mesh layout (MainPlan::layout; set per attempt by the host together with what the last
 	// workgroup of k_main then reports, cleared by run_main): then k_main is the run's only launch.  layoutRan: the launch was
-	// made that way (read by the host behind run_block_lists, which launches nothing then).
-	bool keepLayout = false, layoutRan = false;
+	// made that way (read by the host behind run_block_lists, which launches nothing then).  keepIndices: such a launch also
+	// keeps the index pool (MainPlan::layout 2; asked for with the layout); indicesKept: the launch was made that way.
+	bool keepLayout = false, layoutRan = false, keepIndices = false, indicesKept = false;
 	LayoutEnd layoutEnd = {};
-	void set_layout_end(const u32 cursors[2], const u32* totals, u32* lists)
+	void set_layout_end(const u32 cursors[2], const u32* totals, u32* lists, bool indices)
 	{
+		keepIndices = indices;
 		layoutEnd = LayoutEnd();
 		layoutEnd.cursors[0] = cursors[0]; layoutEnd.cursors[1] = cursors[1];
 		for (u32 l = 0; l < MAX_LEVELS; ++l) layoutEnd.totals[l] = totals[l];
@@ -3811,7 +3818,7 @@ struct Backend {
 	{
 		ResetRanges r;
 		pendingClean = alreadyClean;
-		keepLayout = layoutRan = false; // (every attempt starts here: asked for behind this by set_layout_end, granted by run_main)
+		keepLayout = layoutRan = keepIndices = indicesKept = false; // (every attempt starts here: asked for behind this by set_layout_end, granted by run_main)
 		for (u32 l = 0; l < MAX_LEVELS; ++l) r.maps[l] = p.levels[l].slotOf;
 		u32 run = headerWords;
 		r.header = header; r.headerWords = headerWords;
@@ -4092,8 +4099,8 @@ struct Backend {
 		for (u32 l = 1; l < levels; ++l) items += (unsigned long long)p.levels[l].cap * ((mode == 3u ? 0u : 1u) + (l < plan.fastEnd ? 1u : 0u) + (p.levels[l].hasTransitions ? 1u : 0u));
 		if (withLevel0) items += p.levels[0].cap;
 		matModeUsed = 0;
-		const bool layoutAsked = keepLayout;
-		keepLayout = layoutRan = false;
+		const bool layoutAsked = keepLayout, indicesAsked = keepIndices;
+		keepLayout = layoutRan = keepIndices = indicesKept = false;
 		if (!items) return;
 		// persistent workgroups; without the level-0 queue at most as many as the previous run had items (the host's hint; any
 		// number is correct - a workgroup that finds the queues empty leaves - but every workgroup costs a dequeue)
@@ -4111,7 +4118,8 @@ struct Backend {
 			// would follow k_main, and nothing of k_tail's work is left but what LayoutEnd describes.
 			LayoutEnd end = LayoutEnd();
 			if (layoutAsked && mode == 3u && keepSlots && clockStart && publish.host && nextSeed.header && levels <= (u32)PYRAMID_LEVELS && !stageOn) {
-				plan.layout = 1u;
+				plan.layout = indicesAsked ? 2u : 1u;
+				indicesKept = indicesAsked;
 				end = layoutEnd;
 				end.pub = publish;
 				end.seed = nextSeed;

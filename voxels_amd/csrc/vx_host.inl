@@ -133,6 +133,11 @@ struct vx_ctx {
 	bool layoutOn = false, layoutValid = false;
 	u32 layoutLevels = 0, layoutCursors[2] = { 0, 0 }, layoutTotals[MAX_LEVELS] = {};
 	uint64_t layoutRuns[2] = { 0, 0 };
+	// A run that keeps the layout also keeps the index pool's bytes (MainPlan::layout 2; vx_polygonize lists the pool's
+	// writers).  VX_KEEP_INDICES=0: it rewrites them.  indexKeepRuns: layout-kept attempts that rewrote the indices | kept
+	// them (vx_index_keep_counts).
+	bool indexKeepOn = false;
+	uint64_t indexKeepRuns[2] = { 0, 0 };
 	u32 listWgs = 0;
 	void* haloBuf[4] = { nullptr, nullptr, nullptr, nullptr }; // staging of the halo messages: send below, send above, receive from below, receive from above
 	size_t haloCap[4] = { 0, 0, 0, 0 };
@@ -941,6 +946,8 @@ int vx_ctx_create(int device_index, vx_ctx** out)
 	c->matInPlaceOn = c->be.tune.matInPlace != 0;
 	// VX_LAYOUT=0: a run in place is still followed by k_tail
 	c->layoutOn = c->be.tune.layout != 0;
+	// VX_KEEP_INDICES=0: a run that keeps the layout still rewrites the index pool
+	c->indexKeepOn = c->be.tune.keepIndices != 0;
 	if (c->planOn) c->headerSet[2] = c->be.alloc((HDR_WORDS + HDR_PARTIALS) * 4);
 	if (c->planOn && !c->headerSet[2]) { vx_ctx_destroy(c); return VX_ERR_DEVICE; }
 #endif
@@ -1841,6 +1848,27 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 		//   * vx_device_block_table's upload of listed[]: only behind incremental runs (no device lists), whose plan is gone.
 		// Nothing in it depends on the material LUT: counts and offsets come from case codes, vertex reuse and the pool ranges;
 		// the LUT row only enters pack_vertex_regs, as the texture bytes of a vertex (so vx_material_lut keeps the layout).
+		//
+		// With indexKeepOn a layout-kept attempt also vouches for the INDEX POOL (Pools::idx; MainPlan::layout 2): every index
+		// range a record names holds the bytes this attempt would store, so its table-driven bodies store none.  An index is a
+		// vertex base of the layout plus an ordinal from case codes and reuse decisions - the grid's signs and material ids, not
+		// the LUT.  Everything that stores into the pool, and what becomes of the layout then:
+		//   * f0_walk, f1_block, trf_block (TV_STREAM_STORE of a triangle's three indices) and tr_phase_flush_indices in the
+		//     general phases of tr_block: inside k_main.  The attempt that left the layout wrote every range through them; a
+		//     layout-kept attempt writes the same bytes to the same places (layout 1), or only tr_block's general phases do
+		//     (layout 2).  A layout miss is followed by its two-launch repeat, which is not layout-kept and rewrites every range;
+		//   * reg_phase_flush_indices / tr_phase_flush_indices in regular0_pass, regular_pass and k_transition, and the index
+		//     stores of k_regular0 (vx_regular0.inl), k_regular0_fast, k_regular1_fast and their k_dirty_ forms: the general
+		//     passes behind HDR_SLOW / HDR_LARGE, the chain of launches, partial and incremental runs - none is layout-kept; the
+		//     first two leave no layout, the chain and partial runs are no planRun, incremental runs go through slot_plan_drop;
+		//   * k_copy_segments with the pool as destination: vx_compact_pools (into the spare pool, which then becomes the pool) -
+		//     drops the layout.  vx_download_level's gathered download copies FROM the pool into a buffer of its own;
+		//   * ensure_pools when it replaces the pool (drops the layout) and grow_pools_keeping (a d2d copy into a larger pool;
+		//     only vx_polygonize_dirty calls it, which drops the plan).
+		// No query or edit module stores into it: ray casts, shape casts, overlap queries and scatter take Pools::idx as a pointer
+		// to const (vx_ray.inl, vx_shape.inl, vx_overlap.inl, vx_scatter.inl); occlusion, LOD selection, stamps, undo records,
+		// brushes, smoothing, islands, walk fields, measurements and height maps never see the pool.  vx_device_meshes and
+		// vx_export_meshes hand the caller pointers to const: the pools are read-only outside this library.
 		layoutKept = kept && c->be.matMode == 3u && c->layoutOn && c->layoutValid && c->layoutLevels == levels;
 		if (!layoutKept) layout_drop(c);
 #endif
@@ -1882,7 +1910,7 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 			c->hdrPinned[HDR_PUBLISHED] = 0; // (see below)
 			pubReady = c->be.lists_publish_header(c->hdrPinned, (const u32*)c->dHeader, HDR_WORDS, (u32*)c->dHeader + HDR_PUBLISHED);
 			RunClock::tag(c->be, HDR_PUBLISHED, c->runEpoch, byClock ? (u32)HDR_CLOCK1 : 0u);
-			c->be.set_layout_end(c->layoutCursors, c->layoutTotals, (u32*)c->dHeader + HDR_LISTS);
+			c->be.set_layout_end(c->layoutCursors, c->layoutTotals, (u32*)c->dHeader + HDR_LISTS, c->indexKeepOn);
 		}
 #endif
 		run_pipeline(c, p, levels);
@@ -1922,6 +1950,7 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 			oneLaunch = c->be.layoutRan;
 			if (!oneLaunch) layout_drop(c); // (the launches of this attempt rewrite records and lists)
 			if (kept) ++c->layoutRuns[oneLaunch ? 1 : 0];
+			if (oneLaunch) ++c->indexKeepRuns[c->be.indicesKept ? 1 : 0];
 #endif
 			c->be.stage_mark(7);
 		}
@@ -2764,6 +2793,14 @@ int vx_layout_keep_counts(vx_ctx* c, uint64_t out[2])
 	VX_ENTER_RUN(c); // (host counters)
 	if (!c || !out) return fail(c, VX_ERR_INVALID, "vx_layout_keep_counts: null argument");
 	out[0] = c->layoutRuns[0]; out[1] = c->layoutRuns[1];
+	return VX_OK;
+}
+
+int vx_index_keep_counts(vx_ctx* c, uint64_t out[2])
+{
+	VX_ENTER_RUN(c); // (host counters)
+	if (!c || !out) return fail(c, VX_ERR_INVALID, "vx_index_keep_counts: null argument");
+	out[0] = c->indexKeepRuns[0]; out[1] = c->indexKeepRuns[1];
 	return VX_OK;
 }
 #endif

@@ -77,6 +77,13 @@ struct MainPlan {
 	// (layout_ranges, vx_hip.hip) instead of reserving them, checks its totals against the record's counts, and stores
 	// neither record nor list count nor - level 0 - the slot's bitmaps; nobody builds lists behind the kernel, and its last
 	// workgroup does what is left of k_tail (LayoutEnd).  Uniform at run time, like matMode.
+	// 2: the same, and the run keeps the INDEX POOL's bytes too (main_indices_kept).  An index is its cell's vertex base plus an
+	// ordinal, or its owner's: the bases are the layout (the record's vOff and the scan of the per-cell counts), the ordinals
+	// come from case codes and reuse decisions - signs and material ids of the grid, which has not changed or the plan and the
+	// layout would be gone - and nothing in them depends on the material table.  The table-driven bodies (f0_walk, f1_block,
+	// trf_block) cannot drop a triangle, so their cell phase alone yields the index counts that layout_ranges checks against
+	// the record; they write no triangle descriptor, run no triangle lane and store no index.  The general phases of tr_block
+	// (a zero on a staged plane: the degenerate filter decides the count) write their indices as ever - the same bytes.
 	u32 layout;
 };
 
@@ -127,6 +134,7 @@ __device__ __forceinline__ const MainKernargs& main_kernargs()
 	return *(const MainKernargs*)kp;
 }
 __device__ __forceinline__ bool main_layout_kept() { return r0_uniform(main_kernargs().plan.layout) != 0u; }
+__device__ __forceinline__ bool main_indices_kept() { return r0_uniform(main_kernargs().plan.layout) == 2u; }
 
 // DIRTY: the incremental run's form (TransVoxelRun::Execute with a Modification, src/TransVoxelImpl.cpp:429-465): the same two
 // queues over the work lists k_dirty_head wrote - level-0 blocks with the bitmaps the head formed (no SELF), material blocks
