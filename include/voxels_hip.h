@@ -848,10 +848,11 @@ int vx_download_level(vx_ctx* ctx, uint32_t level, vx_block_info* infos, vx_vert
                       vx_vertex* tverts, uint32_t* tidx);
 /* Device-resident hand-off (renderer interop): the meshes stay in two device pools; a block's meshes are contiguous
  * ranges of them.  A full run that hands out pool ranges rewrites both pools; a full run that keeps the mesh layout
- * (vx_layout_keep_counts out[1]) rewrites every vertex where it was and leaves the index pool's bytes alone
- * (vx_index_keep_counts) - they are what it would store; an incremental run appends the rebuilt blocks behind what is there
+ * (vx_layout_keep_counts out[1]) leaves the index pool's bytes alone (vx_index_keep_counts) - they are what it would store -
+ * and of the regular vertices it rewrites only the texture bytes, tex[8], where they were (vx_geometry_keep_counts; position,
+ * secondary position, secW and normal are what it would store; transition vertices are rewritten whole); an incremental run appends the rebuilt blocks behind what is there
  * (ranges of kept blocks stay valid, ranges of replaced blocks become garbage until the next full run).  The pools are
- * read-only for the caller, as the const pointers say: a kept run relies on the index bytes it finds.  d_verts /
+ * read-only for the caller, as the const pointers say: a kept run relies on the index and geometry bytes it finds.  d_verts /
  * d_indices are valid until the next run on this context (an incremental run may move the pools when it has to grow
  * them); indices are relative to the start of their own mesh, exactly as downloaded. */
 typedef struct vx_block_ranges {
@@ -1257,8 +1258,8 @@ int vx_slot_plan_counts(vx_ctx* ctx, uint64_t out[2]);
  * launches: out[0] = two, k_main and k_tail, out[1] = one, k_main alone - a run in place (vx_material_inplace_counts out[1]) on
  * slots whose last accepted run left its mesh layout behind: every block's record, the block lists with their totals and the
  * pool cursors, which depend on the grid, the BF_Empty flags, the level count and the slot plan alone (not on the material
- * table: vx_material_lut keeps the layout).  Such a run rewrites every vertex where its record says it was, leaves the index
- * pool's bytes alone (vx_index_keep_counts; the pools are read-only for the caller), rebuilds no list, and
+ * table: vx_material_lut keeps the layout).  Such a run rewrites the texture bytes of every regular vertex, and every
+ * transition vertex whole, where its record says they were (vx_geometry_keep_counts), leaves the index pool's bytes alone (vx_index_keep_counts; the pools are read-only for the caller), rebuilds no list, and
  * its last workgroup publishes the header.  Whatever drops the slot plan drops the layout, and so do vx_compact_pools, pools
  * that had to grow, and a run that handed a block to the general passes or met the large capacity class.
  * VX_LAYOUT=0 (read at context creation) keeps no layout: every kept run is two launches.
@@ -1270,13 +1271,26 @@ int vx_layout_keep_counts(vx_ctx* ctx, uint64_t out[2]);
 /* Full-run attempts of this context that kept the mesh layout (vx_layout_keep_counts out[1], since the context was created) by
  * what they did with the index pool: out[0] = rewrote every index, out[1] = kept the indices - the pool already holds, byte for
  * byte, what the run would store: an index is a vertex base of the kept layout plus an ordinal that follows from the signs and
- * material ids of the unchanged grid, and nothing in it depends on the material table.  Such a run computes and stores every
- * vertex as always (the texture bytes of a vertex do depend on the table), checks every block's index count against its record,
+ * material ids of the unchanged grid, and nothing in it depends on the material table.  Such a run computes and stores the
+ * texture bytes of every vertex (they do depend on the table; the rest of a vertex: vx_geometry_keep_counts), checks every block's index count against its record,
  * and neither forms nor stores the indices of the table-driven blocks; a transition block with an exact zero on a staged plane
  * still writes its (unchanged) indices.  Whatever drops the layout ends it: the next run rewrites the pool.
  * VX_KEEP_INDICES=0 (read at context creation): every run that keeps the layout rewrites the indices.
  * Diagnostics: pool contents, block tables, statistics and vx_exec_info are the same either way.  HIP builds only. */
 int vx_index_keep_counts(vx_ctx* ctx, uint64_t out[2]);
+
+/* Full-run attempts of this context that kept the mesh layout (vx_layout_keep_counts out[1], since the context was created) by
+ * what they did with the regular vertices: out[0] = computed and stored whole vertices, out[1] = texture bytes only - bytes
+ * 0..39 of a vertex (position, secondary position, secW, normal) are a function of the grid alone, which cannot have changed
+ * while a layout is valid, and the pool holds them where the block's record says; bytes 40..47 (tex[8]) are the one part the
+ * material table enters, and vx_material_lut is the real-use reason to run again on an unchanged grid.  Such a run computes the
+ * texture bytes of every regular vertex afresh - the blend byte too: an invalid table row forces it to 0 - and rewrites them
+ * with one 8-byte store per vertex; it reads no gradient, normalises nothing and forms no position.  Transition vertices
+ * (8.6 % of all on the bench terrain) are written whole as ever, the same bytes.  Whatever drops the layout ends it: the next
+ * run rewrites every vertex whole.
+ * VX_KEEP_GEOMETRY=0 (read at context creation): every run that keeps the layout computes and stores whole vertices.
+ * Diagnostics: pool contents, block tables, statistics and vx_exec_info are the same either way.  HIP builds only. */
+int vx_geometry_keep_counts(vx_ctx* ctx, uint64_t out[2]);
 
 /* The device forms of the exactness-critical arithmetic checked exhaustively on the GPU they run on (the reference does
  * this arithmetic on the host: t = (v1 << 8) / (v1 - v0), src/TransVoxelImpl.cpp:1591; normalizeFixZero, :93-103):

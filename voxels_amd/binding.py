@@ -319,6 +319,10 @@ class HipLibrary:
         self.has_index_keep = hasattr(lib, "vx_index_keep_counts")
         if self.has_index_keep:
             lib.vx_index_keep_counts.argtypes = [vp, vp]
+        # (the regular vertices' geometry kept by runs that keep the layout: HIP builds only, and absent from builds made before it)
+        self.has_geometry_keep = hasattr(lib, "vx_geometry_keep_counts")
+        if self.has_geometry_keep:
+            lib.vx_geometry_keep_counts.argtypes = [vp, vp]
         lib.vx_selftest.argtypes = [vp, vp]
         lib.vx_stage_layout.argtypes = [vp, C.POINTER(C.c_int)]
         lib.vx_set_stage_timing.argtypes = [vp, C.c_int]
@@ -1475,4 +1479,14 @@ class Polygonizer:
             raise VoxelsHipError("this library has no vx_index_keep_counts")
         out = np.zeros(2, np.uint64)
         self._check(self._lib.vx_index_keep_counts(self._h, _ptr(out)), "vx_index_keep_counts")
+        return int(out[0]), int(out[1])
+
+    def geometry_keep_counts(self):
+        """vx_geometry_keep_counts: (whole vertices stored, texture bytes only) - the full-run attempts of this context that kept the
+        mesh layout, by what they did with the regular vertices, cumulative.  HIP builds only: the CPU emulation library has no such
+        entry point."""
+        if not self._L.has_geometry_keep:
+            raise VoxelsHipError("this library has no vx_geometry_keep_counts")
+        out = np.zeros(2, np.uint64)
+        self._check(self._lib.vx_geometry_keep_counts(self._h, _ptr(out)), "vx_geometry_keep_counts")
         return int(out[0]), int(out[1])

@@ -61,7 +61,8 @@ GXX_TARGETS = {
     "walk_host": ("tests/walk/libvoxels_walk_host.so", ["tests/walk/walk_host.cpp"], [], [], []),
     "undo_host": ("tests/undo/libvoxels_undo_host.so", ["tests/undo/undo_host.cpp"], ["-ffp-contract=off"], [], []),
     "stamp_host": ("tests/stamp/libvoxels_stamp_host.so", ["tests/stamp/stamp_host.cpp"], ["-ffp-contract=off"], [], []),
-    "measure_host": ("tests/measure/libvoxels_measure_host.so", ["tests/measure/measure_host.cpp", "tests/height/height_host.cpp", "tests/occlusion/occlusion_host.cpp"], ["-ffp-contract=off"], [], []),
+    "measure_host": ("tests/measure/libvoxels_measure_host.so", ["tests/measure/measure_host.cpp", "tests/height/height_host.cpp", "tests/occlusion/occlusion_host.cpp", "tests/geomkeep/geomkeep_host.cpp"],
+                     ["-ffp-contract=off", "-Wno-unknown-pragmas", "-Wno-subobject-linkage"], [], []),
     "smooth_host": ("tests/smooth/libvoxels_smooth_host.so", ["tests/smooth/smooth_host.cpp"], ["-ffp-contract=off", "-Wno-unknown-pragmas"], [], []),
     "scatter_host": ("tests/scatter/libvoxels_scatter_host.so", ["tests/scatter/scatter_host.cpp"], ["-ffp-contract=off", "-Wno-unknown-pragmas"], [], []),
     "overlap_host": ("tests/overlap/libvoxels_overlap_host.so", ["tests/overlap/overlap_host.cpp"], ["-ffp-contract=off", "-Wno-unknown-pragmas"], [], []),
@@ -322,7 +323,10 @@ def build_measure_host(force=False):
     (tests/occlusion/occlusion_host.cpp): the rule of csrc/tv_occlusion.h in a plain loop over vertices and the dense grid, and the
     kernel's pipeline - staged row masks of a block's neighbourhood, then the probes, with the region's reach as a parameter so that
     the reads from the grid itself are reached - the entry checks and the layout of the header's structs (tests/test_occlusion.py,
-    tests/test_abi_occlusion.py)."""
+    tests/test_abi_occlusion.py).  And the comparison of the texture-only vertex forms with the full ones
+    (tests/geomkeep/geomkeep_host.cpp): the CPU emulation of tests/emu, whose every full run walks its table-driven regular blocks
+    once more with the serial forms and compares, vertex by vertex, the 8 bytes of f0_vertex_tex / f1_vertex_tex with bytes 40..47
+    of the full form (tests/test_geometry_keep_host.py)."""
     return _build_shared("measure_host", force)
 
 

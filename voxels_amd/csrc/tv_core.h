@@ -413,6 +413,26 @@ TV_HD unsigned long long lut_row(const u8* lut, u32 materialId)
 	return row;
 }
 
+// The texture bytes of a packed vertex, PolyVertex::tex[8], as its dwords 10 and 11 (little-endian): the ONLY part of a vertex
+// that depends on the material table.  mat = id | blend << 8 (RawVertex::mat), row = the table row of the vertex's cell.
+// tex = {0, blend, Ids1[1], Ids0[1] | Ids1[2], Ids1[0], Ids0[2], Ids0[0]}, all zero where the row is not valid - the blend
+// byte too, so it is computed afresh whenever the table may have changed.  One definition for pack_vertex_regs, the host
+// branch of pack_vertex_row and the texture-only vertex forms (f0_vertex_tex, f1_vertex_tex).
+TV_HD void pack_tex_dwords(u32 mat, unsigned long long row, u32& t0, u32& t1)
+{
+	const u32 lo = (u32)row, hi = (u32)(row >> 32);
+	const bool ok = ((hi >> 16) & 0xFFu) != 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+	// picked out of the row with two byte permutes (selector 0..3 = low dword, 4..7 = high dword, 0x0C = constant 0)
+	t0 = __builtin_amdgcn_perm(hi, lo, 0x01040C0Cu) | (((mat >> 8) & 0xFFu) << 8);
+	t1 = __builtin_amdgcn_perm(hi, lo, 0x00020305u);
+#else
+	t0 = (((mat >> 8) & 0xFFu) << 8) | ((hi & 0xFFu) << 16) | (((lo >> 8) & 0xFFu) << 24);             // Uxz = Ids1[1], Txz = Ids0[1]
+	t1 = ((hi >> 8) & 0xFFu) | ((lo >> 24) << 8) | (((lo >> 16) & 0xFFu) << 16) | ((lo & 0xFFu) << 24); // Uny = Ids1[2], Upy = Ids1[0], Tny = Ids0[2], Tpy = Ids0[0]
+#endif
+	if (!ok) { t0 = 0; t1 = 0; }
+}
+
 #if defined(__HIPCC__)
 // a packed vertex in registers: the twelve dwords of a PolyVertex (three 16-byte pieces); device code only
 struct VertexRegs { u32 w[12]; };
@@ -422,13 +442,8 @@ __device__ __forceinline__ void pack_vertex_regs(const RawVertex& r, unsigned lo
 	const float k = 1.f / 256.f;
 	u32 f = r.flags;
 	if (f) f = (f >> 3) | ((f & 7u) << 3);
-	// texture bytes {0, blend, Ids1[1], Ids0[1] | Ids1[2], Ids1[0], Ids0[2], Ids0[0]} picked out of the row with two
-	// byte permutes (selector 0..3 = low dword, 4..7 = high dword, 0x0C = constant 0)
-	const u32 lo = (u32)row, hi = (u32)(row >> 32);
-	const bool ok = ((hi >> 16) & 0xFFu) != 0;
-	u32 t0 = __builtin_amdgcn_perm(hi, lo, 0x01040C0Cu) | (((r.mat >> 8) & 0xFFu) << 8);
-	u32 t1 = __builtin_amdgcn_perm(hi, lo, 0x00020305u);
-	if (!ok) { t0 = 0; t1 = 0; }
+	u32 t0, t1;
+	pack_tex_dwords(r.mat, row, t0, t1);
 	o.w[0] = __float_as_uint(r.p[0] * k); o.w[1] = __float_as_uint(r.p[2] * k); o.w[2] = __float_as_uint(r.p[1] * k); o.w[3] = __float_as_uint(r.s[0] * k);
 	o.w[4] = __float_as_uint(r.s[2] * k); o.w[5] = __float_as_uint(r.s[1] * k); o.w[6] = f; o.w[7] = __float_as_uint(r.n[0]);
 	o.w[8] = __float_as_uint(r.n[1]); o.w[9] = __float_as_uint(r.n[2]); o.w[10] = t0; o.w[11] = t1;
@@ -462,18 +477,9 @@ TV_HD void pack_vertex_row(const RawVertex& r, unsigned long long row, PolyVerte
 	o.sec[0] = r.s[0] * k; o.sec[1] = r.s[2] * k; o.sec[2] = r.s[1] * k;
 	o.secW = f;
 	o.nrm[0] = r.n[0]; o.nrm[1] = r.n[1]; o.nrm[2] = r.n[2];
-	u8 e[8];
-#pragma unroll
-	for (int i = 0; i < 8; ++i) e[i] = (u8)(row >> (8 * i));
-	const bool ok = e[6] != 0;
-	o.tex[0] = 0;
-	o.tex[1] = ok ? (u8)(r.mat >> 8) : 0;
-	o.tex[2] = ok ? e[4] : 0; // Uxz = Ids1[1]
-	o.tex[3] = ok ? e[1] : 0; // Txz = Ids0[1]
-	o.tex[4] = ok ? e[5] : 0; // Uny = Ids1[2]
-	o.tex[5] = ok ? e[3] : 0; // Upy = Ids1[0]
-	o.tex[6] = ok ? e[2] : 0; // Tny = Ids0[2]
-	o.tex[7] = ok ? e[0] : 0; // Tpy = Ids0[0]
+	u32 t[2];
+	pack_tex_dwords(r.mat, row, t[0], t[1]);
+	memcpy(o.tex, t, 8);
 	*out = o;
 #endif
 }
@@ -482,6 +488,22 @@ TV_HD void pack_vertex_row(const RawVertex& r, unsigned long long row, PolyVerte
 struct VertexToMemory {
 	PolyVertex* out;
 	TV_HD void operator()(const RawVertex& r, unsigned long long row) const { pack_vertex_row(r, row, out); }
+};
+// Where the texture bytes of a texture-only vertex go: one aligned 8-byte store at byte 40 of its record, whose first 40
+// bytes - position, secondary position, secW, normal - stay what the run that left the mesh layout wrote
+struct TexToMemory {
+	PolyVertex* out;
+	TV_HD void operator()(u32 t0, u32 t1) const
+	{
+#if defined(__HIP_DEVICE_COMPILE__)
+		typedef u32 __attribute__((ext_vector_type(2))) v2u;
+		const v2u t = { t0, t1 };
+		TV_STREAM_STORE((v2u*)out + 5, t);
+#else
+		const u32 t[2] = { t0, t1 };
+		memcpy(out->tex, t, 8);
+#endif
+	}
 };
 
 TV_HD void pack_vertex(const RawVertex& r, const u8* lut, PolyVertex* out) { pack_vertex_row(r, lut_row(lut, r.mat), out); }

@@ -260,6 +260,32 @@ TV_HD void f0_vertex(const ST& st, const F0Tables& T, u32 desc, int ox, int oy, 
 	f0_vertex(st, T, desc, ox, oy, oz, lutRow, VertexToMemory{ out });
 }
 
+// ---- one lane = one new vertex, its texture bytes alone (a run that keeps the mesh layout, MainPlan::geometry 1) -----
+// Bytes 0..39 of a vertex - position, secondary position, secW, normal - are a function of the grid, which has not changed
+// while a layout is valid; bytes 40..47 are pack_tex_dwords of rv.mat and the cell's table row, and the table is what such a
+// run's real use changes (vx_material_lut).  So: the two end samples for t, the six material / blend bytes, the rv.mat rule
+// of f0_vertex - no gradient stencil, nothing normalised, no position.  The sink gets the two texture dwords.
+template <typename ST, typename SINK>
+TV_HD void f0_vertex_tex(const ST& st, const F0Tables& T, u32 desc, unsigned long long lutRow, const SINK& sink)
+{
+	const u32 c = desc & 0xFFFu;
+	const F0Edge e = T.edge[desc >> 12];
+	const int cx = (int)(c & 15u), cy = (int)((c >> 4) & 15u), cz = (int)(c >> 8);
+	const i8* s0 = st.samp + samp_index(cx, cy, cz) + (e.x & 0xFFFFu);
+	const int val0 = s0[0], val1 = s0[e.x >> 16];
+	const int mo = cz * F0_MPLANE + cy * F0_MROW + cx;
+	const int m0 = mo + (int)(e.y & 0x3FFu), m1 = m0 + (int)((e.y >> 10) & 0x3FFu);
+	const u32 cellId = st.matId[mo], cellBlend = st.blend[mo];
+	const u32 id0 = st.matId[m0], id1 = st.matId[m1], b0 = st.blend[m0], b1 = st.blend[m1];
+	const int t = edge_t_crossing(val0, val1), u = 256 - t;
+	u32 mat;
+	if (id0 == id1 && id0 == cellId) mat = id0 | (((((u32)t & 0x1FFu) * b0 + ((u32)u & 0x1FFu) * b1) >> 8) << 8);
+	else mat = cellId | (cellBlend << 8);
+	u32 t0, t1;
+	pack_tex_dwords(mat, lutRow, t0, t1);
+	sink(t0, t1);
+}
+
 // ---- one lane = one triangle of the chunk: its three indices --------------------------------------------------------
 // A created vertex is the cell's vertex base plus its rank among the cell's created vertices; a reused one comes from the
 // stored slot ordinal of the owner cell (direction and slot are properties of the edge).  Both forms are evaluated for

@@ -125,6 +125,46 @@ TV_HD bool f1_vertex(const ST& st, const F0Tables& T, const SMP& smp, const u16*
 	return f1_vertex(st, T, smp, blockCache, desc, level, ox, oy, oz, lutRow, VertexToMemory{ out });
 }
 
+// ---- one lane = one new vertex, its texture bytes alone (f0_vertex_tex; a run with MainPlan::geometry 1) -------------
+// The chain walk to the level-0 edge stays - it finds the two voxels whose materials the vertex reads, the samples t comes
+// from, and whether the chain ended on a voxel - and so do M0, M1 and the cell's cache entry.  The twelve gradient fetches
+// around the two end points, the normals, the positions, the boundary flags and finish_secondary do not.  Returns what
+// f1_vertex returns: "strictly inside its level-0 edge".
+template <typename ST, typename SMP, typename SINK>
+TV_HD bool f1_vertex_tex(const ST& st, const F0Tables& T, const SMP& smp, const u16* blockCache, u32 desc, int level, int ox, int oy, int oz, unsigned long long lutRow, const SINK& sink)
+{
+	const u32 c = desc & 0xFFFu;
+	const F0Edge e = T.edge[desc >> 12];
+	const int cx = (int)(c & 15u), cy = (int)((c >> 4) & 15u), cz = (int)(c >> 8);
+	const int mult = 1 << level;
+	const i8* s0 = st.samp + (cz * F1_SPLANE + cy * F1_SROW + cx) + (e.z & 0xFFFFu);
+	int p0 = s0[0], p1 = s0[e.z >> 16];
+	const u32 v0 = (e.y >> 20) & 7u, axis = (e.y >> 23) & 3u;
+	const int ax = axis == 0u ? 1 : 0, ay = axis == 1u ? 1 : 0, az = axis == 2u ? 1 : 0;
+	int x0 = ox + (cx + (int)(v0 & 1u)) * mult, y0 = oy + (cy + (int)((v0 >> 1) & 1u)) * mult, z0 = oz + (cz + (int)(v0 >> 2)) * mult;
+	int len = mult;
+	for (int lev = level; lev > 0; --lev) {
+		const int h = len >> 1;
+		const int mx = x0 + ax * h, my = y0 + ay * h, mz = z0 + az * h;
+		const int midV = smp.dist(smp.tx(mx) + smp.ty(my) + smp.tz(mz));
+		if (p0 * midV <= 0) p1 = midV;
+		else { x0 = mx; y0 = my; z0 = mz; p0 = midV; }
+		len = h;
+	}
+	const u32 M0 = smp.mat(smp.tx(x0) + smp.ty(y0) + smp.tz(z0), x0, y0, z0);
+	const u32 M1 = smp.mat(smp.tx(x0 + ax) + smp.ty(y0 + ay) + smp.tz(z0 + az), x0 + ax, y0 + ay, z0 + az);
+	const u32 cellMat = TV_LOAD_THROUGH(&blockCache[c]);
+	const bool interior = p0 * p1 < 0;
+	const int t = (p0 != p1) ? edge_t_crossing(p0, p1) : 0, u = 256 - t;
+	u32 mat;
+	if ((M0 & 0xFFu) == (M1 & 0xFFu) && (M0 & 0xFFu) == (cellMat & 0xFFu)) mat = (M0 & 0xFFu) | (((((u32)t & 0x1FFu) * (M0 >> 8) + ((u32)u & 0x1FFu) * (M1 >> 8)) >> 8) << 8);
+	else mat = cellMat;
+	u32 t0, t1;
+	pack_tex_dwords(mat, lutRow, t0, t1);
+	sink(t0, t1);
+	return interior;
+}
+
 #if !defined(__HIPCC__)
 // ---- CPU emulation of one block (tests/emu).  false: the block belongs to the general pass (a zero lattice sample, or
 //      a chain ended on a voxel); nothing of the result was written then except the pool cursors, which only grow.

@@ -397,7 +397,9 @@ __device__ __forceinline__ void f0_walk(const F0Tables& T, Fast0State<CAP>& st, 
 						if (j < vEnd) {
 							const u32 desc = st.vdesc[j], c = desc & 0xFFFu;
 							const u32 cellId = st.matId[(c >> 8) * F0_MPLANE + ((c >> 4) & 15u) * F0_MROW + (c & 15u)];
-							f0_vertex(st, T, desc, ox, oy, oz, K::lut_row_waterfall(p.G.lut, cellId), vOut + j);
+							// (the run keeps the regular vertices' geometry, MainPlan::geometry, read where it decides: texture bytes alone)
+							if (MAP && main_geometry_kept()) f0_vertex_tex(st, T, desc, K::lut_row_waterfall(p.G.lut, cellId), TexToMemory{ vOut + j });
+							else f0_vertex(st, T, desc, ox, oy, oz, K::lut_row_waterfall(p.G.lut, cellId), vOut + j);
 						}
 						if (j < tEnd) {
 							u32 ids[3];

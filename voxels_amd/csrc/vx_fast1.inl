@@ -228,7 +228,10 @@ __device__ __forceinline__ void f1_block(const ExecParamsDev& p, const F0Tables&
 				if (j < vEnd) {
 					const u32 desc = st.vdesc[j];
 					const unsigned long long lut = K::lut_row_waterfall(p.G.lut, (u32)st.cacheId[desc & 0xFFFu]);
-					if (!f1_vertex(st, T, smp, L.cache + (size_t)slot * BLOCK_CELLS, desc, (int)level, ox, oy, oz, lut, vOut + j)) notInterior = 1;
+					// (the run keeps the regular vertices' geometry, MainPlan::geometry, read where it decides: texture bytes alone)
+					if (GATED && main_geometry_kept()) {
+						if (!f1_vertex_tex(st, T, smp, L.cache + (size_t)slot * BLOCK_CELLS, desc, (int)level, ox, oy, oz, lut, TexToMemory{ vOut + j })) notInterior = 1;
+					} else if (!f1_vertex(st, T, smp, L.cache + (size_t)slot * BLOCK_CELLS, desc, (int)level, ox, oy, oz, lut, vOut + j)) notInterior = 1;
 				}
 				if (j < tEnd) {
 					u32 ids[3];

@@ -92,6 +92,9 @@ __device__ __forceinline__ const ExecParamsDev& kernarg_params()
 // (Defined in vx_main.inl, behind MainPlan.)
 __device__ __forceinline__ bool main_layout_kept();
 __device__ __forceinline__ bool main_indices_kept();
+// main_geometry_kept: MainPlan::geometry - the run keeps bytes 0..39 of the regular vertices too: f0_walk and f1_block run the
+// texture-only vertex forms.  Read the same way, in the trip loops, around the call of the vertex body.
+__device__ __forceinline__ bool main_geometry_kept();
 
 constexpr int WG = 256;
 constexpr int REG_CAP_SMALL = LARGE_THRESHOLD; // LDS capacity class of the regular pass that covers ordinary surfaces
@@ -3417,6 +3420,7 @@ struct Backend {
 		u32 matInPlace = 1;  // VX_MAT_INPLACE=0: a run that keeps the slot plan still copies the material caches from the store into their slots
 		u32 layout = 1;      // VX_LAYOUT=0: a run in place still reserves its pool ranges and is followed by k_tail (two launches, not one)
 		u32 keepIndices = 1; // VX_KEEP_INDICES=0: a run that keeps the mesh layout still rewrites the index pool (MainPlan::layout 1, not 2)
+		u32 keepGeometry = 1; // VX_KEEP_GEOMETRY=0: a run that keeps the mesh layout still computes and stores whole regular vertices (MainPlan::geometry 0, not 1)
 		// fixed since round 6 (were environment variables while they were being measured; profiles/HISTORY.md has the sweeps)
 		static constexpr u32 classifyRowGroup = 4, regWgsPerCu = 20, f1WgsPerCu = 20, foldBlocks = 65536, upWgsPerCu = 5, mainWgsPerCu = 4, mainBatch = 2, mainUpperNum = 1, mainUpperDen = 4;
 		bool fast0() const { return (fast & 1u) != 0; }
@@ -3456,6 +3460,7 @@ struct Backend {
 		tune.matInPlace = env_u32("VX_MAT_INPLACE", 1);
 		tune.layout = env_u32("VX_LAYOUT", 1);
 		tune.keepIndices = env_u32("VX_KEEP_INDICES", 1);
+		tune.keepGeometry = env_u32("VX_KEEP_GEOMETRY", 1);
 		hipDeviceProp_t prop;
 		if (hipGetDeviceProperties(&prop, device) == hipSuccess) cus = prop.multiProcessorCount;
 		if (!check(hipStreamCreateWithFlags(&ownStream, hipStreamNonBlocking), "hipStreamCreate")) { err = lastError; return false; }
@@ -3801,11 +3806,13 @@ struct Backend {
 	// workgroup of k_main then reports, cleared by run_main): then k_main is the run's only launch.  layoutRan: the launch was
 	// made that way (read by the host behind run_block_lists, which launches nothing then).  keepIndices: such a launch also
 	// keeps the index pool (MainPlan::layout 2; asked for with the layout); indicesKept: the launch was made that way.
-	bool keepLayout = false, layoutRan = false, keepIndices = false, indicesKept = false;
+	// keepGeometry / geometryKept: the same for the geometry of the regular vertices (MainPlan::geometry 1).
+	bool keepLayout = false, layoutRan = false, keepIndices = false, indicesKept = false, keepGeometry = false, geometryKept = false;
 	LayoutEnd layoutEnd = {};
-	void set_layout_end(const u32 cursors[2], const u32* totals, u32* lists, bool indices)
+	void set_layout_end(const u32 cursors[2], const u32* totals, u32* lists, bool indices, bool geometry)
 	{
 		keepIndices = indices;
+		keepGeometry = geometry;
 		layoutEnd = LayoutEnd();
 		layoutEnd.cursors[0] = cursors[0]; layoutEnd.cursors[1] = cursors[1];
 		for (u32 l = 0; l < MAX_LEVELS; ++l) layoutEnd.totals[l] = totals[l];
@@ -3818,7 +3825,7 @@ struct Backend {
 	{
 		ResetRanges r;
 		pendingClean = alreadyClean;
-		keepLayout = layoutRan = keepIndices = indicesKept = false; // (every attempt starts here: asked for behind this by set_layout_end, granted by run_main)
+		keepLayout = layoutRan = keepIndices = indicesKept = keepGeometry = geometryKept = false; // (every attempt starts here: asked for behind this by set_layout_end, granted by run_main)
 		for (u32 l = 0; l < MAX_LEVELS; ++l) r.maps[l] = p.levels[l].slotOf;
 		u32 run = headerWords;
 		r.header = header; r.headerWords = headerWords;
@@ -4099,8 +4106,8 @@ struct Backend {
 		for (u32 l = 1; l < levels; ++l) items += (unsigned long long)p.levels[l].cap * ((mode == 3u ? 0u : 1u) + (l < plan.fastEnd ? 1u : 0u) + (p.levels[l].hasTransitions ? 1u : 0u));
 		if (withLevel0) items += p.levels[0].cap;
 		matModeUsed = 0;
-		const bool layoutAsked = keepLayout, indicesAsked = keepIndices;
-		keepLayout = layoutRan = keepIndices = indicesKept = false;
+		const bool layoutAsked = keepLayout, indicesAsked = keepIndices, geometryAsked = keepGeometry;
+		keepLayout = layoutRan = keepIndices = indicesKept = keepGeometry = geometryKept = false;
 		if (!items) return;
 		// persistent workgroups; without the level-0 queue at most as many as the previous run had items (the host's hint; any
 		// number is correct - a workgroup that finds the queues empty leaves - but every workgroup costs a dequeue)
@@ -4120,6 +4127,8 @@ struct Backend {
 			if (layoutAsked && mode == 3u && keepSlots && clockStart && publish.host && nextSeed.header && levels <= (u32)PYRAMID_LEVELS && !stageOn) {
 				plan.layout = indicesAsked ? 2u : 1u;
 				indicesKept = indicesAsked;
+				plan.geometry = geometryAsked ? 1u : 0u;
+				geometryKept = geometryAsked;
 				end = layoutEnd;
 				end.pub = publish;
 				end.seed = nextSeed;

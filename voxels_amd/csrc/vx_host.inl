@@ -138,6 +138,11 @@ struct vx_ctx {
 	// them (vx_index_keep_counts).
 	bool indexKeepOn = false;
 	uint64_t indexKeepRuns[2] = { 0, 0 };
+	// ... and the geometry of the regular vertices (MainPlan::geometry 1; vx_polygonize lists the vertex pool's writers): only
+	// their texture bytes are computed and stored.  VX_KEEP_GEOMETRY=0: whole vertices.  geometryKeepRuns: layout-kept attempts
+	// that stored whole vertices | texture bytes only (vx_geometry_keep_counts).
+	bool geometryKeepOn = false;
+	uint64_t geometryKeepRuns[2] = { 0, 0 };
 	u32 listWgs = 0;
 	void* haloBuf[4] = { nullptr, nullptr, nullptr, nullptr }; // staging of the halo messages: send below, send above, receive from below, receive from above
 	size_t haloCap[4] = { 0, 0, 0, 0 };
@@ -948,6 +953,8 @@ int vx_ctx_create(int device_index, vx_ctx** out)
 	c->layoutOn = c->be.tune.layout != 0;
 	// VX_KEEP_INDICES=0: a run that keeps the layout still rewrites the index pool
 	c->indexKeepOn = c->be.tune.keepIndices != 0;
+	// VX_KEEP_GEOMETRY=0: a run that keeps the layout still computes and stores whole vertices
+	c->geometryKeepOn = c->be.tune.keepGeometry != 0;
 	if (c->planOn) c->headerSet[2] = c->be.alloc((HDR_WORDS + HDR_PARTIALS) * 4);
 	if (c->planOn && !c->headerSet[2]) { vx_ctx_destroy(c); return VX_ERR_DEVICE; }
 #endif
@@ -1869,6 +1876,30 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 		// to const (vx_ray.inl, vx_shape.inl, vx_overlap.inl, vx_scatter.inl); occlusion, LOD selection, stamps, undo records,
 		// brushes, smoothing, islands, walk fields, measurements and height maps never see the pool.  vx_device_meshes and
 		// vx_export_meshes hand the caller pointers to const: the pools are read-only outside this library.
+		//
+		// With geometryKeepOn a layout-kept attempt vouches for bytes 0..39 of every REGULAR vertex in the VERTEX POOL as well
+		// (Pools::verts; MainPlan::geometry 1): position, secondary position, secW and normal are functions of the grid alone
+		// (f0_vertex, f1_vertex: samples, the chain walk, boundary flags from the cell's place), every vertex of a regular range
+		// a record names lies where this attempt would put it, and so f0_walk and f1_block compute and store bytes 40..47 only,
+		// the texture bytes - the one part the LUT enters (pack_tex_dwords).  Everything that stores into the pool:
+		//   * f0_walk and f1_block (pack_vertex_row's three 16-byte stores, or TexToMemory's one 8-byte store), trf_block
+		//     (trf_vertex) and tr_emit_vertex in the general phases of tr_block: inside k_main.  The attempt that left the layout
+		//     wrote every range whole through them; a layout-kept attempt writes the same bytes to the same places - whole
+		//     vertices (geometry 0, and always the transition ranges), or the texture bytes of the regular ones (geometry 1).  A
+		//     layout miss (a total that differs from its record, a block handed on, f1_block's suspect chain) is followed by its
+		//     two-launch repeat, which is not layout-kept and rewrites every range whole;
+		//   * reg_phase_emit / the vertex phases of regular0_pass, regular_pass and k_transition (tv_block.h, vx_regular0.inl),
+		//     k_regular0_fast, k_regular1_fast and their k_dirty_ forms: the general passes behind HDR_SLOW / HDR_LARGE, the chain
+		//     of launches, partial and incremental runs - none is layout-kept and all write whole vertices; the first two leave
+		//     no layout, the chain and partial runs are no planRun, incremental runs go through slot_plan_drop;
+		//   * k_copy_segments with the pool as destination: vx_compact_pools (into the spare pool, which then becomes the pool) -
+		//     drops the layout.  vx_download_level's gathered download copies FROM the pool into a buffer of its own;
+		//   * ensure_pools when it replaces the pool (drops the layout) and grow_pools_keeping (a d2d copy into a larger pool;
+		//     only vx_polygonize_dirty calls it, which drops the plan).
+		// No query or edit module stores into it: ray casts, shape casts, overlap queries, scatter and occlusion take Pools::verts
+		// as a pointer to const (vx_ray.inl, vx_shape.inl, vx_overlap.inl, vx_scatter.inl, vx_occlusion.inl - occlusion writes
+		// an array of its own beside the pool); LOD selection, stamps, undo records, brushes, smoothing, islands, walk fields,
+		// measurements and height maps never see the pool.
 		layoutKept = kept && c->be.matMode == 3u && c->layoutOn && c->layoutValid && c->layoutLevels == levels;
 		if (!layoutKept) layout_drop(c);
 #endif
@@ -1910,7 +1941,7 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 			c->hdrPinned[HDR_PUBLISHED] = 0; // (see below)
 			pubReady = c->be.lists_publish_header(c->hdrPinned, (const u32*)c->dHeader, HDR_WORDS, (u32*)c->dHeader + HDR_PUBLISHED);
 			RunClock::tag(c->be, HDR_PUBLISHED, c->runEpoch, byClock ? (u32)HDR_CLOCK1 : 0u);
-			c->be.set_layout_end(c->layoutCursors, c->layoutTotals, (u32*)c->dHeader + HDR_LISTS, c->indexKeepOn);
+			c->be.set_layout_end(c->layoutCursors, c->layoutTotals, (u32*)c->dHeader + HDR_LISTS, c->indexKeepOn, c->geometryKeepOn);
 		}
 #endif
 		run_pipeline(c, p, levels);
@@ -1951,6 +1982,7 @@ int vx_polygonize_from(vx_ctx* c, uint32_t num_levels, uint32_t first_meshed_lev
 			if (!oneLaunch) layout_drop(c); // (the launches of this attempt rewrite records and lists)
 			if (kept) ++c->layoutRuns[oneLaunch ? 1 : 0];
 			if (oneLaunch) ++c->indexKeepRuns[c->be.indicesKept ? 1 : 0];
+			if (oneLaunch) ++c->geometryKeepRuns[c->be.geometryKept ? 1 : 0];
 #endif
 			c->be.stage_mark(7);
 		}
@@ -2801,6 +2833,14 @@ int vx_index_keep_counts(vx_ctx* c, uint64_t out[2])
 	VX_ENTER_RUN(c); // (host counters)
 	if (!c || !out) return fail(c, VX_ERR_INVALID, "vx_index_keep_counts: null argument");
 	out[0] = c->indexKeepRuns[0]; out[1] = c->indexKeepRuns[1];
+	return VX_OK;
+}
+
+int vx_geometry_keep_counts(vx_ctx* c, uint64_t out[2])
+{
+	VX_ENTER_RUN(c); // (host counters)
+	if (!c || !out) return fail(c, VX_ERR_INVALID, "vx_geometry_keep_counts: null argument");
+	out[0] = c->geometryKeepRuns[0]; out[1] = c->geometryKeepRuns[1];
 	return VX_OK;
 }
 #endif

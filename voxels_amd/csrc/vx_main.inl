@@ -85,6 +85,13 @@ struct MainPlan {
 	// the record; they write no triangle descriptor, run no triangle lane and store no index.  The general phases of tr_block
 	// (a zero on a staged plane: the degenerate filter decides the count) write their indices as ever - the same bytes.
 	u32 layout;
+	// 1 (only with layout != 0; main_geometry_kept): the run keeps the GEOMETRY of the regular vertices too - bytes 0..39 of a
+	// vertex (position, secondary position, secW, normal) are a function of the grid alone, which has not changed or the layout
+	// would be gone, and they lie where the record says.  f0_walk and f1_block then run the texture-only vertex forms
+	// (f0_vertex_tex, f1_vertex_tex): the material rule and the table row - the one thing vx_material_lut changes - and one
+	// 8-byte store at byte 40 of the record.  trf_block and the general phases of tr_block write whole vertices as ever, the
+	// same bytes.  0: whole vertices everywhere.  Uniform at run time.
+	u32 geometry;
 };
 
 // The end of a run that keeps the mesh layout (MainPlan::layout; pub.host == nullptr in every other run, which ends as ever):
@@ -135,6 +142,7 @@ __device__ __forceinline__ const MainKernargs& main_kernargs()
 }
 __device__ __forceinline__ bool main_layout_kept() { return r0_uniform(main_kernargs().plan.layout) != 0u; }
 __device__ __forceinline__ bool main_indices_kept() { return r0_uniform(main_kernargs().plan.layout) == 2u; }
+__device__ __forceinline__ bool main_geometry_kept() { return r0_uniform(main_kernargs().plan.geometry) != 0u; }
 
 // DIRTY: the incremental run's form (TransVoxelRun::Execute with a Modification, src/TransVoxelImpl.cpp:429-465): the same two
 // queues over the work lists k_dirty_head wrote - level-0 blocks with the bitmaps the head formed (no SELF), material blocks
